@@ -68,6 +68,8 @@ struct sp_query {
   int rows_j0 = 0, rows_nj = 0;  // sp_query_begin_for_db on a row shard: only these first-dimension rows were expanded
   const sp_db* for_sparse = nullptr;  // begun for this sparse bucket: only the rows holding items were expanded
   std::shared_ptr<const sp_db::SparseIndex> sparse_index;  // ... with this snapshot of its index (kept until the query is freed)
+  std::shared_ptr<const DevBuf<u64>> planar;  // the digit-planar copy a batched group's pass on this (first) workspace reads: pinned
+                                              // until the query is freed, i.e. until after its stream has been synchronised
   float ms[4] = {0, 0, 0, 0};
   bool streams_idle = false;  // the owner has waited for the main stream after the last enqueue (which orders stream2's work before it)
   ~sp_query() {
@@ -124,24 +126,107 @@ void download_raw(Workspace& W, const u64* src, size_t words, uint64_t* host) {
   HIP_CHECK(hipStreamSynchronize(W.stream));
 }
 
+// the fold buffers of a stage-level fold export grown to `num_per` ciphertexts and `further` levels (the workspace was sized for
+// the params' own num_per)
+void ensure_stage_fold(Workspace& W, size_t num_per, size_t further) {
+  const size_t two_t = 2 * W.P->t_gsw;
+  W.ensure_expand();
+  W.foldX.ensure(num_per * 2 * POLY_LEN);
+  W.foldY.ensure(std::max<size_t>(num_per / 2, 1) * 2 * POLY_LEN);
+  W.fold_dig.ensure(num_per * two_t * 2 * POLY_LEN);
+  W.fold_ntt.ensure(std::max<size_t>(num_per / 2, 1) * 2 * 2 * POLY_LEN);
+  W.fold_mats.ensure(further * 2 * 2 * two_t * 2 * POLY_LEN);
+}
+
 void check_device(int dev) {
   int cur = 0;
   HIP_CHECK(hipGetDevice(&cur));
   if (cur != dev) throw ArgError("handle belongs to HIP device " + std::to_string(dev) + " but the current device is " + std::to_string(cur));
 }
 
+// what one workspace of a batched group may need, as the group planner and the planar copy estimate it: three times the
+// first-dimension output (a rough bound; pooled workspaces only make it conservative)
+size_t group_ws_bytes(const Params& p, int np_local) { return (size_t)3 * p.planes() * 4 * POLY_LEN * (size_t)np_local * sizeof(u32); }
+
+// bits per plaintext coefficient (ceil log2 p) and bytes of an item per plane (params.rs:188-193) of the database encoder
+size_t pt_bits(const Params& p) {
+  size_t logp = 0;
+  while (((u64)1 << logp) < p.pt_modulus) logp++;
+  return logp;
+}
+size_t chunk_bytes(const Params& p) { return (p.db_item_size + p.planes() - 1) / p.planes(); }
+
+// the encoder's view of `d`; the call sites add the window (win*, file_len), the row pairs (jp0, njp) and the single-item fields
+DbEncodeDesc encode_desc(const sp_db& d) {
+  const Params& p = d.params->p;
+  DbEncodeDesc e{};
+  e.db = d.words.p;
+  e.db_item_size = (int)p.db_item_size;
+  e.bytes_per_chunk = (int)chunk_bytes(p);
+  e.logp = (int)pt_bits(p);
+  e.pt_modulus = (u32)p.pt_modulus;
+  e.planes = (int)p.planes();
+  e.num_per = d.np_local;
+  e.cm = d.colmap();
+  e.dim0 = (int)p.dim0();
+  e.j0 = d.j0;
+  e.nj = d.nj;
+  e.packed = d.packed;
+  e.only_item = -1;
+  return e;
+}
+
+// one item's bytes, zero padded to db_item_size, in the handle's upload buffer (caller holds mu)
+const uint8_t* upload_item(sp_db& d, const uint8_t* data, size_t len) {
+  const size_t n = d.params->p.db_item_size;
+  d.upload.ensure(std::max<size_t>(n, 1));
+  HIP_CHECK(hipMemset(d.upload.p, 0, n));
+  if (len) h2d_sync(d.upload.p, data, len);
+  return d.upload.p;
+}
+
+using PlanarPin = std::shared_ptr<const DevBuf<u64>>;
+
+// One batched pass of the group qs[0 .. B) over `db`, run on the first query's stream: the database, the queries' operands and
+// outputs; on the matrix cores the group's query digit table with the first workspace (allocated on its first batched call, then
+// reused) and, for two query tiles, the digit-planar copy -- pinned in `pin`, which the caller holds until that stream has been
+// synchronised.
+SweepBatchDesc group_pass(const sp_db& db, sp_query_t* const* qs, int B, bool use_planar, PlanarPin& pin) {
+  const Params& p = db.params->p;
+  Workspace& W0 = *qs[0]->ws;
+  SweepBatchDesc d{};
+  d.db = db.words.p;
+  d.batch = B;
+  d.planes = (int)p.planes();
+  d.num_per = db.np_local;
+  d.dim0 = (int)p.dim0();
+  d.j0 = db.j0;
+  d.nj = db.nj;
+  for (int i = 0; i < B; i++) {
+    d.qv[i] = qs[i]->ws->qv.p;
+    d.out[i] = qs[i]->ws->sweep_out.p;
+  }
+  if (sweep_batch_wants_mfma(d)) {
+    W0.batch_rq.ensure(sweep_batch_rq_words(d.nj, sweep_batch_tiles(d.batch)));
+    d.rq = W0.batch_rq.p;
+    if (use_planar && sweep_batch_tiles(d.batch) == 2) pin = const_cast<sp_db&>(db).ensure_planar(W0.stream);
+  }
+  d.planar = pin ? reinterpret_cast<const unsigned char*>(pin->p) : nullptr;
+  return d;
+}
+
 }  // namespace
 
 // The digit-planar copy of a PACKED, unsharded database (sweep_planar.hpp): what the 9 .. 16-query pass reads.  Built by
 // sp_db_prepare_batch (at load time) or on first use (one gather pass over the PACKED units), only when the device has the room for
-// a second copy (8 bytes per word) beside the workspaces of two groups; nullptr = keep to the PACKED kernels.
-const unsigned char* sp_db::ensure_planar(hipStream_t s) {
+// a second copy (8 bytes per word) beside the workspaces of two groups; null = keep to the PACKED kernels.
+std::shared_ptr<const DevBuf<u64>> sp_db::ensure_planar(hipStream_t s) {
   std::lock_guard<std::mutex> lk(mu);
-  if (tunable("batch_planar", 1) == 0) {   // switched off: the copy's memory goes back too
+  if (tunable("batch_planar", 1) == 0) {   // switched off: the copy's memory goes back too (once no pass holds it)
     drop_planar();
     return nullptr;
   }
-  if (planar_state == 1) return reinterpret_cast<const unsigned char*>(planar.p);
+  if (planar_state == 1) return planar;
   if (planar_state == -1) return nullptr;
   const Params& p = params->p;
   if (!packed || sparse || num_shards != 1 || col_G != 1 || !sweep_planar_shape_ok(np_local, nj)) {
@@ -150,25 +235,23 @@ const unsigned char* sp_db::ensure_planar(hipStream_t s) {
   }
   planar_state = -2;   // until the copy stands: a shortfall of memory is looked at again next time
   const size_t bytes = sweep_planar_bytes((int)p.planes(), np_local, nj);
-  if (planar.n * sizeof(u64) < bytes) {
+  if (!planar) {   // (a copy that is not valid and not dropped is no pass's: rebuilt in place)
     size_t fr = 0, tot = 0;
-    // room for the copy + the workspaces of two groups of 16 (three times the first-dimension output each, as the group planner
-    // estimates) + 4 GiB
-    const size_t per_ws = (size_t)3 * p.planes() * 4 * POLY_LEN * (size_t)np_local * sizeof(u32);
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < bytes + 32 * per_ws + ((size_t)4 << 30)) {
+    // room for the copy + the workspaces of two groups of 16 + 4 GiB
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < bytes + 32 * group_ws_bytes(p, np_local) + ((size_t)4 << 30)) {
       (void)hipGetLastError();
       return nullptr;
     }
     try {
-      planar.alloc((bytes + 7) / 8);
+      planar = std::make_shared<DevBuf<u64>>((bytes + 7) / 8);
     } catch (const OomError&) {
       return nullptr;
     }
   }
-  launch_packed_to_planar(reinterpret_cast<unsigned char*>(planar.p), words.p, (int)p.planes(), np_local, nj, s);
+  launch_packed_to_planar(reinterpret_cast<unsigned char*>(planar->p), words.p, (int)p.planes(), np_local, nj, s);
   HIP_CHECK(hipStreamSynchronize(s));
   planar_state = 1;
-  return reinterpret_cast<const unsigned char*>(planar.p);
+  return planar;
 }
 
 // present items by column + the expansion schedule pruned to the rows that hold items: rebuilt when a NEW key has been
@@ -377,7 +460,11 @@ sp_db_t* sp_db_create(const sp_params_t* h, int shard, int num_shards) { return 
 sp_db_t* sp_db_create_columns(const sp_params_t* h, int shard, int num_shards) { return db_create_impl(h, shard, num_shards, true); }
 void sp_db_free(sp_db_t* d) { delete d; }
 size_t sp_db_device_bytes(const sp_db_t* d) { return d ? (d->sparse ? d->polys.bytes() : d->words.bytes()) : 0; }
-size_t sp_db_batch_copy_bytes(const sp_db_t* d) { return d ? d->planar.bytes() : 0; }
+size_t sp_db_batch_copy_bytes(const sp_db_t* d) {
+  if (!d) return 0;
+  std::lock_guard<std::mutex> lk(const_cast<sp_db*>(d)->mu);
+  return d->planar_state == 1 ? d->planar->bytes() : 0;
+}
 
 int sp_db_load_plane(sp_db_t* d, int plane, int z0, int nz, const uint64_t* words) {
   return guarded([&] {
@@ -386,24 +473,16 @@ int sp_db_load_plane(sp_db_t* d, int plane, int z0, int nz, const uint64_t* word
     const Params& p = d->params->p;
     need(plane >= 0 && (size_t)plane < p.planes() && z0 >= 0 && nz >= 0 && (size_t)(z0 + nz) <= POLY_LEN, "bad plane / z range");
     check_device(d->device);
-    std::lock_guard<std::mutex> lk(d->mu);
-    struct DropAfter {   // on every path out, after the last write to `words` has completed (mu held)
-      sp_db* d;
-      ~DropAfter() { d->drop_planar(); }
-    } drop_after{d};
+    sp_db::WriteScope write(*d);
     const size_t row_words = p.num_per() * p.dim0();
-    const size_t max_stage = ((size_t)64 << 20) / 8;  // 64 MiB staging
+    const size_t max_stage = ((size_t)64 << 20) / 8;  // 64 MiB windows
     const int zs = (int)std::max<size_t>(1, std::min<size_t>((size_t)nz, max_stage / row_words));
-    // the upload window: ONE device buffer per handle, kept (db_stage_keep, default 1) -- not one allocation per call
-    // (profiles/r06_stale_staging.md)
-    DevBuf<u64> local;
-    const bool keep = tunable("db_stage_keep", 1) != 0;
-    DevBuf<u64>& stage = keep ? d->load_stage : local;
-    stage.ensure((size_t)zs * row_words);
+    d->upload.ensure((size_t)zs * row_words * 8);
+    const u64* stage = reinterpret_cast<const u64*>(d->upload.p);
     for (int z = 0; z < nz; z += zs) {
       const int cnt = std::min(zs, nz - z);
-      h2d_sync(stage.p, words + (size_t)z * row_words, (size_t)cnt * row_words * 8);
-      launch_db_relayout(d->words.p, plane, stage.p, z0 + z, cnt, d->np_local, (int)p.dim0(), d->j0, d->nj,
+      h2d_sync(d->upload.p, words + (size_t)z * row_words, (size_t)cnt * row_words * 8);
+      launch_db_relayout(d->words.p, plane, stage, z0 + z, cnt, d->np_local, (int)p.dim0(), d->j0, d->nj,
                          d->packed, d->colmap(), 0);
       HIP_CHECK(hipDeviceSynchronize());
     }
@@ -436,15 +515,8 @@ int sp_db_load_items(sp_db_t* d, const uint8_t* file, size_t file_len) {
     sp_params* h = const_cast<sp_params*>(d->params);
     const Params& p = h->p;
     DeviceState& D = h->device_state();
-    std::lock_guard<std::mutex> lk(d->mu);
-    struct DropAfter {
-      sp_db* d;
-      ~DropAfter() { d->drop_planar(); }
-    } drop_after{d};
-    size_t logp = 0;
-    while (((u64)1 << logp) < p.pt_modulus) logp++;
-    const size_t chunks = p.planes();
-    const size_t bpc = (p.db_item_size + chunks - 1) / chunks;  // ceil, params.rs:188-193
+    sp_db::WriteScope write(*d);
+    const size_t logp = pt_bits(p), chunks = p.planes(), bpc = chunk_bytes(p);
     need((bpc * 8 + logp - 1) / logp <= POLY_LEN, "item chunk does not fit one polynomial (server.rs:292)");
     need(logp >= 1 && logp <= 28, "plaintext modulus out of range");
     // windows of whole row pairs: the rows' items are contiguous in the file
@@ -457,34 +529,21 @@ int sp_db_load_items(sp_db_t* d, const uint8_t* file, size_t file_len) {
     // of a window.  The spill is chunks * bpc - db_item_size bytes, which exceeds one chunk when
     // db_item_size < (chunks - 1) * bpc (5-byte items in 4 chunks: bpc = 2, spill = 3).
     const size_t tail = std::max(bpc, chunks * bpc - p.db_item_size);
-    DevBuf<uint8_t> win((size_t)pairs_per_win * 2 * row_bytes + tail);
+    d->upload.ensure((size_t)pairs_per_win * 2 * row_bytes + tail);   // kept: up to db_load_window + tail per handle
     for (int jp = 0; jp < npairs_total; jp += pairs_per_win) {
       const int cnt = std::min(pairs_per_win, npairs_total - jp);
       const size_t item0 = (size_t)(d->j0 + 2 * jp) * p.num_per();
       const size_t off = item0 * p.db_item_size;
       size_t want = (size_t)cnt * 2 * row_bytes + tail;
       size_t have = off < file_len ? std::min(want, file_len - off) : 0;
-      if (have) h2d_sync(win.p, file + off, have);
-      DbEncodeDesc e{};
-      e.win = win.p;
+      if (have) h2d_sync(d->upload.p, file + off, have);
+      DbEncodeDesc e = encode_desc(*d);
+      e.win = d->upload.p;
       e.win_item0 = item0;
       e.win_bytes = have;
       e.file_len = file_len;
-      e.db = d->words.p;
-      e.db_item_size = (int)p.db_item_size;
-      e.bytes_per_chunk = (int)bpc;
-      e.logp = (int)logp;
-      e.pt_modulus = (u32)p.pt_modulus;
-      e.planes = (int)p.planes();
-      e.num_per = d->np_local;
-      e.cm = d->colmap();
-      e.dim0 = (int)p.dim0();
-      e.j0 = d->j0;
-      e.nj = d->nj;
-      e.packed = d->packed;
       e.jp0 = jp;
       e.njp = cnt;
-      e.only_item = -1;
       launch_db_encode(D.T, e, 0);
       HIP_CHECK(hipDeviceSynchronize());
     }
@@ -503,9 +562,7 @@ int sp_db_update_item(sp_db_t* d, size_t item_idx, const uint8_t* data, size_t l
       // lib/server/src/db/loading.rs:317-359 update_item_raw + sparse_db.rs:42-48 upsert
       DeviceState& D = h->device_state();
       std::lock_guard<std::mutex> lk(d->mu);
-      size_t logp = 0;
-      while (((u64)1 << logp) < p.pt_modulus) logp++;
-      const size_t planes = p.planes(), bpc = (p.db_item_size + planes - 1) / planes, poly_words = planes * POLY_LEN;
+      const size_t planes = p.planes(), poly_words = planes * POLY_LEN;
       auto it = d->slot_of.find(item_idx);
       size_t slot;
       bool new_key = false;
@@ -531,11 +588,8 @@ int sp_db_update_item(sp_db_t* d, size_t item_idx, const uint8_t* data, size_t l
         }
         d->slot_of[item_idx] = slot;
       }
-      d->staging.ensure(std::max<size_t>(p.db_item_size, 1));   // reused across updates
-      HIP_CHECK(hipMemsetAsync(d->staging.p, 0, p.db_item_size, 0));
-      if (len) h2d_sync(d->staging.p, data, len);
-      launch_sparse_item_encode(D.T, d->staging.p, (int)p.db_item_size, (int)bpc, (int)logp, (u32)p.pt_modulus,
-                                d->polys.p + slot * poly_words, (int)planes, 0);
+      launch_sparse_item_encode(D.T, upload_item(*d, data, len), (int)p.db_item_size, (int)chunk_bytes(p), (int)pt_bits(p),
+                                (u32)p.pt_modulus, d->polys.p + slot * poly_words, (int)planes, 0);
       HIP_CHECK(hipDeviceSynchronize());
       if (new_key) d->index_dirty = true;   // an overwrite (the reference's upsert of an existing key) leaves the index alone
       return;
@@ -545,34 +599,11 @@ int sp_db_update_item(sp_db_t* d, size_t item_idx, const uint8_t* data, size_t l
     if ((int)(ii % (size_t)d->col_G) != d->col_g) return;   // column lives on another shard
     DeviceState& D = h->device_state();
     std::lock_guard<std::mutex> lk(d->mu);
-    size_t logp = 0;
-    while (((u64)1 << logp) < p.pt_modulus) logp++;
-    const size_t chunks = p.planes();
-    const size_t bpc = (p.db_item_size + chunks - 1) / chunks;
-    // the item's bytes on the device: the handle's own staging buffer, reused across updates -- never a fresh allocation per
-    // update (a buffer that is freed and allocated again at the same address between kernels is what one XCD's workgroups can
-    // read the PREVIOUS contents of when several processes share the GPU: profiles/r06_stale_staging.md)
-    d->staging.ensure(std::max<size_t>(p.db_item_size, 1));
-    uint8_t* const win = d->staging.p;
-    HIP_CHECK(hipMemset(win, 0, p.db_item_size));
-    if (len) h2d_sync(win, data, len);
-    DbEncodeDesc e{};
-    e.win = win;
+    DbEncodeDesc e = encode_desc(*d);
+    e.win = upload_item(*d, data, len);
     e.win_item0 = item_idx;
     e.win_bytes = p.db_item_size;
     e.file_len = (item_idx + 1) * p.db_item_size;  // the record itself is complete (zero padded)
-    e.db = d->words.p;
-    e.db_item_size = (int)p.db_item_size;
-    e.bytes_per_chunk = (int)bpc;
-    e.logp = (int)logp;
-    e.pt_modulus = (u32)p.pt_modulus;
-    e.planes = (int)p.planes();
-    e.num_per = d->np_local;
-    e.cm = d->colmap();
-    e.dim0 = (int)p.dim0();
-    e.j0 = d->j0;
-    e.nj = d->nj;
-    e.packed = d->packed;
     e.jp0 = (int)(j - d->j0) / 2;
     e.njp = 1;
     e.only_item = (long)item_idx;
@@ -581,7 +612,7 @@ int sp_db_update_item(sp_db_t* d, size_t item_idx, const uint8_t* data, size_t l
     // a planar copy follows the item: its 8 entries per (plane, z), regathered from the words just written (same stream) -- an
     // upsert costs 64 KiB of writes, not a 64 GiB rebuild by the next group of 9 .. 16 queries
     if (d->planar_state == 1)
-      launch_planar_patch_item(reinterpret_cast<unsigned char*>(d->planar.p), d->words.p, (int)p.planes(), d->np_local, d->nj,
+      launch_planar_patch_item(reinterpret_cast<unsigned char*>(d->planar->p), d->words.p, (int)p.planes(), d->np_local, d->nj,
                                (int)j - d->j0, (int)(ii / (size_t)d->col_G), 0);
     HIP_CHECK(hipDeviceSynchronize());
   });
@@ -592,11 +623,7 @@ int sp_db_fill_synthetic(sp_db_t* d, uint64_t seed) {
     need(d != nullptr, "null db");
     need(!d->sparse, "a sparse bucket is filled through sp_db_update_item");
     check_device(d->device);
-    std::lock_guard<std::mutex> lk(d->mu);
-    struct DropAfter {
-      sp_db* d;
-      ~DropAfter() { d->drop_planar(); }
-    } drop_after{d};
+    sp_db::WriteScope write(*d);
     const Params& p = d->params->p;
     launch_db_synth(d->words.p, seed, (int)p.planes(), d->np_local, (int)p.dim0(), d->j0, d->nj, d->packed, d->colmap(), 0);
     HIP_CHECK(hipDeviceSynchronize());
@@ -610,8 +637,8 @@ int sp_db_prepare_batch(sp_db_t* d, int* built) {
   return guarded([&] {
     need(d != nullptr, "null db");
     check_device(d->device);
-    const unsigned char* c = d->sparse ? nullptr : d->ensure_planar(nullptr);
-    if (built) *built = c != nullptr;
+    const bool c = !d->sparse && d->ensure_planar(nullptr);
+    if (built) *built = c;
   });
 }
 uint64_t sp_synth_word(uint64_t seed, uint64_t ref_index) { return synth_word(seed, ref_index); }
@@ -1111,10 +1138,9 @@ int sp_process_query_batch(const sp_params_t* h, const sp_pp_t* const* pps, cons
   group_max = std::max(1, std::min(shape_max, group_max));
   if (group_max > SWEEP_BATCH_MAX && batch > SWEEP_BATCH_MAX) {
     // two groups of 16 hold up to 32 workspaces: keep to groups of 8 when the device could not hold them beside the database
-    // (a rough bound -- three times the first-dimension output per workspace; pooled workspaces only make it conservative)
     size_t fr = 0, tot = 0;
-    const size_t per_ws = (size_t)3 * p.planes() * 4 * POLY_LEN * (size_t)db->np_local * sizeof(u32);
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < (size_t)2 * SWEEP_GROUP_MAX * per_ws) group_max = SWEEP_BATCH_MAX;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < (size_t)2 * SWEEP_GROUP_MAX * group_ws_bytes(p, db->np_local))
+      group_max = SWEEP_BATCH_MAX;
     (void)hipGetLastError();
   }
   stamp("group size decided");
@@ -1180,29 +1206,12 @@ int sp_process_query_batch(const sp_params_t* h, const sp_pp_t* const* pps, cons
         }
       }
       stamp("expansions enqueued");
-      // 2. one database pass for the whole group, on the first query's stream, after the previous group's pass
+      // 2. one database pass for the whole group, on the first query's stream, after the previous group's pass; the first query
+      // holds the pass's pin of the planar copy
       Workspace& W0 = *qs[0]->ws;
-      SweepBatchDesc d{};
-      d.db = db->words.p;
-      d.batch = B;
-      d.planes = (int)p.planes();
-      d.num_per = db->np_local;
-      d.dim0 = (int)p.dim0();
-      d.j0 = db->j0;
-      d.nj = db->nj;
-      for (int i = 0; i < B; i++) {
-        d.qv[i] = qs[i]->ws->qv.p;
-        d.out[i] = qs[i]->ws->sweep_out.p;
-        if (i > 0) HIP_CHECK(hipStreamWaitEvent(W0.stream, qs[i]->ws->ev[1], 0));
-      }
+      for (int i = 1; i < B; i++) HIP_CHECK(hipStreamWaitEvent(W0.stream, qs[i]->ws->ev[1], 0));
       if (prev_pass) HIP_CHECK(hipStreamWaitEvent(W0.stream, prev_pass, 0));
-      // matrix-core form of the pass (sweep_mfma.hpp): the group's query digit table lives with the group's first
-      // workspace (allocated on its first batched call, then reused)
-      if (sweep_batch_wants_mfma(d)) {
-        W0.batch_rq.ensure(sweep_batch_rq_words(d.nj, sweep_batch_tiles(d.batch)));
-        d.rq = W0.batch_rq.p;
-        if (use_planar && sweep_batch_tiles(d.batch) == 2) d.planar = const_cast<sp_db_t*>(db)->ensure_planar(W0.stream);
-      }
+      SweepBatchDesc d = group_pass(*db, qs, B, use_planar, qs[0]->planar);
       sweep_batch_prepare(W0.D->T, d, W0.stream);
       // (a per-plane form of the pass with every query folding plane p beside the pass of plane p + 1 was measured in rounds
       // 2 and 3 and is slower: the pass leaves no registers for a fold workgroup; profiles/r02_fold_batch_experiments.md)
@@ -1242,11 +1251,11 @@ int sp_process_query_batch(const sp_params_t* h, const sp_pp_t* const* pps, cons
     abandon();
     (void)hipGetLastError();
     start = (int)drained;
-    if (step == 1) {
+    if (step == 1) {   // (abandon has released the pins of the groups in flight: dropping the handle's copy frees it)
       sp_db* wdb = const_cast<sp_db_t*>(db);
       std::lock_guard<std::mutex> lk(wdb->mu);
       use_planar = false;
-      if (!wdb->planar.p) continue;   // nothing to give back here: next step
+      if (!wdb->planar) continue;   // nothing to give back here: next step
       wdb->drop_planar();
       wdb->planar_state = -2;
     } else if (step == 2) {
@@ -1310,28 +1319,18 @@ int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, in
       need(qs[i] && qs[i]->state >= 1, "query not begun");
       need(qs[i]->params == db->params, "query and db were created for different params");
     }
-    const Params& p = qs[0]->params->p;
     Workspace& W0 = *qs[0]->ws;
-    SweepBatchDesc d{};
-    d.db = db->words.p;
-    d.batch = batch;
-    d.planes = (int)p.planes();
-    d.num_per = db->np_local;
-    d.dim0 = (int)p.dim0();
-    d.j0 = db->j0;
-    d.nj = db->nj;
     for (int i = 0; i < batch; i++) {
       qs[i]->ws->ensure_sweep();
-      d.qv[i] = qs[i]->ws->qv.p;
-      d.out[i] = qs[i]->ws->sweep_out.p;
       HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream));   // expansions done: the pass is timed alone
       HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream2));
     }
-    if (sweep_batch_wants_mfma(d)) {
-      W0.batch_rq.ensure(sweep_batch_rq_words(d.nj, sweep_batch_tiles(d.batch)));
-      d.rq = W0.batch_rq.p;
-      if (sweep_batch_tiles(d.batch) == 2) d.planar = const_cast<sp_db_t*>(db)->ensure_planar(W0.stream);
-    }
+    PlanarPin pin;   // held for the whole call: on every path out the pass's stream is synchronised before it is released
+    SweepBatchDesc d = group_pass(*db, qs, batch, true, pin);
+    struct Drain {
+      hipStream_t s;
+      ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{W0.stream};
     TimingEvents ev;   // destroyed on every path out of here (launches and HIP_CHECK throw)
     auto pass = [&] {
       sweep_batch_prepare(W0.D->T, d, W0.stream);
@@ -1749,13 +1748,7 @@ int sp_fold_ciphertexts(const sp_params_t* h, uint64_t* cts, size_t num_per, con
     if (further == 0) return;
     const size_t two_t = 2 * p.t_gsw;
     Scoped W(h);
-    W->ensure_expand();
-    // workspace sized for params' own num_per; make sure this call's size fits
-    W->foldX.ensure(num_per * 2 * POLY_LEN);
-    W->foldY.ensure(std::max<size_t>(num_per / 2, 1) * 2 * POLY_LEN);
-    W->fold_dig.ensure(num_per * two_t * 2 * POLY_LEN);
-    W->fold_ntt.ensure(std::max<size_t>(num_per / 2, 1) * 2 * 2 * POLY_LEN);
-    W->fold_mats.ensure(further * 2 * 2 * two_t * 2 * POLY_LEN);
+    ensure_stage_fold(*W, num_per, further);
     DevBuf<u64> tmp;
     DevBuf<u32> dF, dFn;
     upload_ntt(*W, v_folding, further * 2 * two_t * 2 * POLY_LEN, dF, tmp);
@@ -1768,12 +1761,9 @@ int sp_fold_ciphertexts(const sp_params_t* h, uint64_t* cts, size_t num_per, con
         HIP_CHECK(hipMemcpyAsync(row + two_t * 2 * POLY_LEN, dF.p + ((d * 2 + r) * two_t) * 2 * POLY_LEN, two_t * 2 * POLY_LEN * sizeof(u32), hipMemcpyDeviceToDevice, W->stream));
       }
     HIP_CHECK(hipMemcpyAsync(W->foldX.p, cts, num_per * 2 * POLY_LEN * 8, hipMemcpyHostToDevice, W->stream));
-    const long saved = W->fused_min_pairs;
-    W->fused_min_pairs = 1L << 60;  // the stage export honours the caller's v_folding_neg: literal path
-    W->delta_tail = false;
-    u64* res = run_fold(*W, W->foldX.p, W->foldY.p, 1, (int)num_per, -1);
-    W->fused_min_pairs = saved;
-    W->delta_tail = true;
+    W->mats_w_ready = false;   // (whatever wave-layout operands the pooled workspace holds are not this call's)
+    // the stage export honours the caller's v_folding_neg: literal path, every digit
+    u64* res = run_fold(*W, FoldOpts{1L << 60, false, false}, W->foldX.p, W->foldY.p, 1, (int)num_per, -1);
     download_raw(*W, res, 2 * POLY_LEN, cts);
   });
 }
@@ -1789,12 +1779,7 @@ int sp_fold_ciphertexts_fused(const sp_params_t* h, uint64_t* cts, size_t num_pe
     if (further == 0) return;
     const size_t two_t = 2 * p.t_gsw;
     Scoped W(h);
-    W->ensure_expand();
-    W->foldX.ensure(num_per * 2 * POLY_LEN);
-    W->foldY.ensure(std::max<size_t>(num_per / 2, 1) * 2 * POLY_LEN);
-    W->fold_dig.ensure(num_per * two_t * 2 * POLY_LEN);
-    W->fold_ntt.ensure(std::max<size_t>(num_per / 2, 1) * 2 * 2 * POLY_LEN);
-    W->fold_mats.ensure(further * 2 * 2 * two_t * 2 * POLY_LEN);
+    ensure_stage_fold(*W, num_per, further);
     DevBuf<u64> tmp;
     DevBuf<u32> dF;
     upload_ntt(*W, v_folding, further * 2 * two_t * 2 * POLY_LEN, dF, tmp);
@@ -1806,23 +1791,12 @@ int sp_fold_ciphertexts_fused(const sp_params_t* h, uint64_t* cts, size_t num_pe
     launch_folding_neg(W->D->T, W->fold_mats.p, W->D->gadget_gsw.p, (int)further, (int)two_t, W->stream);
     run_mats_to_wave(*W, further);
     HIP_CHECK(hipMemcpyAsync(W->foldX.p, cts, num_per * 2 * POLY_LEN * 8, hipMemcpyHostToDevice, W->stream));
-    const long saved = W->fused_min_pairs;
-    if (fused_min_pairs > 0) W->fused_min_pairs = fused_min_pairs;
     // the caller's ciphertexts: below Q (what the reference's invariants give, and what lets the kernels skip the dead top
     // digit) only if every coefficient says so -- checked here, on the host copy
     bool below_q = true;
     for (size_t i = 0; i < num_per * 2 * POLY_LEN && below_q; i++) below_q = cts[i] < p.modulus;
-    W->fold_inputs_below_q = below_q;
-    u64* res = nullptr;
-    try {
-      res = run_fold(*W, W->foldX.p, W->foldY.p, 1, (int)num_per, -1);
-    } catch (...) {
-      W->fused_min_pairs = saved;
-      W->fold_inputs_below_q = false;
-      throw;
-    }
-    W->fused_min_pairs = saved;
-    W->fold_inputs_below_q = false;
+    const FoldOpts o{fused_min_pairs > 0 ? fused_min_pairs : W->fused_min_pairs, true, below_q};
+    u64* res = run_fold(*W, o, W->foldX.p, W->foldY.p, 1, (int)num_per, -1);
     download_raw(*W, res, 2 * POLY_LEN, cts);
   });
 }

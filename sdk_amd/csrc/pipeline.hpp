@@ -53,15 +53,9 @@ struct Workspace {
   DevBuf<u64> enc_out;       // response bits built on the device
   uint8_t* h_response = nullptr;
   bool host_pinned = true;  // the three staging buffers above come from hipHostMalloc (false: malloc, debug switch ws_pinned)
-  bool delta_tail = true;  // unfused fold levels use the delta form too (false: literal two-matrix form)
-  // true only while run_fold works on ciphertexts the library produced itself (from_ntt / fold outputs: below Q; set by
-  // run_fold_canonical, server.cpp) or on a caller's ciphertexts the stage-level entry point has checked: the fused kernels may
-  // then skip the gadget digits that are identically zero (FoldDesc::t_live).  Default false: raw buffers from a caller or a peer
-  // rank are decomposed in full.
-  bool fold_inputs_below_q = false;
   int out_G = 1;  // column interleave of the sweep output (multi-GPU reduce-scatter path)
   bool zero_shortcuts = false;  // lib/server fold semantics (sparse buckets): set per query, every level fused
-  long fused_min_pairs = 256;  // fold levels with at least this many (pair, plane) units use k_fold_fused
+  long fused_min_pairs = 256;  // fold levels with at least this many (pair, plane) units use k_fold_fused (sizes the digit staging)
 
   Workspace(const Params& P, DeviceState& D);
   ~Workspace();
@@ -95,7 +89,16 @@ void run_sweep_pipelined(Workspace& W, const sp_db& db);
 bool sweep_is_pipelined(const Params& p, const sp_db& db);
 void launch_plane_sweep(Workspace& W, const sp_db& db, size_t plane);
 bool fused_fold_supported(const Params& p);
-u64* run_fold(Workspace& W, u64* X, u64* Y, int np, int num_cts, int top, int d_begin = 0, int d_end = -1);
+// how one run_fold call folds (the query flows build theirs from the workspace: query_fold_opts, server.cpp)
+struct FoldOpts {
+  long fused_min_pairs;  // levels with at least this many (pair, plane) units use the fused kernels
+  bool delta_tail;       // the unfused levels in the delta form too (false: literal two-matrix form, reads G - C)
+  // the inputs are below Q -- ciphertexts the library produced itself (from_ntt / fold outputs) or a caller's that the stage-level
+  // entry point has checked: the fused kernels may then skip the gadget digits that are identically zero (FoldDesc::t_live).
+  // Raw buffers from a caller or a peer rank are decomposed in full.
+  bool inputs_below_q;
+};
+u64* run_fold(Workspace& W, const FoldOpts& o, u64* X, u64* Y, int np, int num_cts, int top, int d_begin = 0, int d_end = -1);
 void run_fold_local(Workspace& W, const u32* reduced_chunk, int G);
 void run_fold_local_plane(Workspace& W, const u32* reduced_plane_chunk, int G, int plane);
 void run_fold_local_join(Workspace& W);

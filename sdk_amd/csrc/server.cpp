@@ -952,7 +952,7 @@ void run_folding_neg(Workspace& W) {
 // What the QUERY path does in get_v_folding_neg's place (server.rs:505-523, 660): nothing but the wave-layout copy of the C halves.
 // Every fold step of this library is the delta form  ct_i + C (*) (G^-1(ct_{i+half}) - G^-1(ct_i))  -- exactly
 // (G - C) (*) ct_i + C (*) ct_{i+half}  mod q0, q1, because G G^-1(x) = x for the unsigned digit slices -- in the fused kernels
-// (fold.hip: kk = two_t + ...) and in the tree tail (run_fold, delta_tail): G - C is never read.  r01-r05 computed it all the same
+// (fold.hip: kk = two_t + ...) and in the tree tail (run_fold, FoldOpts::delta_tail): G - C is never read.  r01-r05 computed it all the same
 // (k_folding_neg, 9-16 us per query, 73 us per 16-query group) and converted both halves to the wave layout.  The stage export
 // sp_get_v_folding_neg still computes it (run_folding_neg), and sp_fold_ciphertexts takes the caller's.
 // Switch fold_neg_materialise = 1: the old behaviour.
@@ -1263,19 +1263,15 @@ void run_sweep_sparse(Workspace& W, const sp_db& db, const int* col_ptr, const i
                       p.db_dim_2 > 0 ? 2 : 1, W.sweep_out.p, (int)p.num_per(), W.stream);
 }
 
-// from_ntt + fold of `np` planes starting at plane pg0 (sweep_out -> final_cts), on W.stream
-// run_fold on ciphertexts this library has just produced itself (from_ntt / fold outputs: canonical, below Q) -- the only callers
-// that may let the fused kernels skip the dead top gadget digit (FoldDesc::t_live).  Everything else (stage-level entry points,
-// ciphertexts gathered from peer ranks or handed in by the caller of the split API) folds with every digit.
-static u64* run_fold_canonical(Workspace& W, u64* X, u64* Y, int np, int num_cts, int top, int d_begin = 0, int d_end = -1) {
-  struct Mark {
-    Workspace& W;
-    explicit Mark(Workspace& w) : W(w) { W.fold_inputs_below_q = true; }
-    ~Mark() { W.fold_inputs_below_q = false; }
-  } mark(W);
-  return run_fold(W, X, Y, np, num_cts, top, d_begin, d_end);
+// The query flows' fold: the workspace's threshold (read when it was created: the digit staging of the unfused levels is sized
+// from it), lowered -- never raised -- by the run-time switch fused_min_pairs_cap (in-process A/B); delta-form tail.  below_q only
+// for ciphertexts this library has just produced itself (from_ntt / fold outputs): everything else (ciphertexts gathered from
+// peer ranks or handed in by the caller of the split API) folds with every digit.
+static FoldOpts query_fold_opts(const Workspace& W, bool below_q) {
+  return FoldOpts{std::min(W.fused_min_pairs, tunable("fused_min_pairs_cap", 1L << 62)), true, below_q};
 }
 
+// from_ntt + fold of `np` planes starting at plane pg0 (sweep_out -> final_cts), on W.stream
 static void fold_planes(Workspace& W, size_t pg0, int np, bool premod) {
   const Params& p = *W.P;
   DeviceState& D = *W.D;
@@ -1292,7 +1288,7 @@ static void fold_planes(Workspace& W, size_t pg0, int np, bool premod) {
     inv.premod = premod ? 1 : 0;
     launch_ntt_inv(D.T, inv, s);
   }
-  u64* res = run_fold_canonical(W, W.foldX.p, W.foldY.p, np, (int)p.num_per(), -1);
+  u64* res = run_fold(W, query_fold_opts(W, true), W.foldX.p, W.foldY.p, np, (int)p.num_per(), -1);
   HIP_CHECK(hipMemcpyAsync(W.final_cts.p + pg0 * 2 * POLY_LEN, res, (size_t)np * 2 * POLY_LEN * sizeof(u64), hipMemcpyDeviceToDevice, s));
 }
 
@@ -1311,7 +1307,7 @@ static int tail_defer_levels(const Params& p, long stop) {  // levels folded per
 static void fold_plane_head(Workspace& W, size_t pl, int levels) {  // from_ntt + the first `levels` levels, parked
   const Params& p = *W.P;
   launch_from_sweep4(W.D->T, W.sweep_out.p + pl * 4 * POLY_LEN * p.num_per(), (int)p.num_per(), 1, 0, W.foldX.p, W.stream);
-  u64* res = run_fold_canonical(W, W.foldX.p, W.foldY.p, 1, (int)p.num_per(), -1, 0, levels);
+  u64* res = run_fold(W, query_fold_opts(W, true), W.foldX.p, W.foldY.p, 1, (int)p.num_per(), -1, 0, levels);
   const size_t cts = p.num_per() >> levels;
   HIP_CHECK(hipMemcpyAsync(W.fold_tail.p + pl * cts * 2 * POLY_LEN, res, cts * 2 * POLY_LEN * sizeof(u64), hipMemcpyDeviceToDevice, W.stream));
 }
@@ -1319,7 +1315,7 @@ static void fold_tails(Workspace& W, int levels) {  // the parked planes togethe
   const Params& p = *W.P;
   const size_t cts = p.num_per() >> levels;
   u64* other = W.fold_tail.p + p.planes() * cts * 2 * POLY_LEN;
-  u64* res = run_fold_canonical(W, W.fold_tail.p, other, (int)p.planes(), (int)p.num_per(), -1, levels, -1);
+  u64* res = run_fold(W, query_fold_opts(W, true), W.fold_tail.p, other, (int)p.planes(), (int)p.num_per(), -1, levels, -1);
   HIP_CHECK(hipMemcpyAsync(W.final_cts.p, res, p.planes() * 2 * POLY_LEN * sizeof(u64), hipMemcpyDeviceToDevice, W.stream));
 }
 
@@ -1383,7 +1379,7 @@ bool fused_fold_supported(const Params& p) { return 4 * p.t_gsw <= 128 && p.bits
 
 // fold_ciphertexts (server.rs:388-427) on `np` planes of `num_cts` raw cts each, dense in X;
 // result ct of plane i ends up at the returned buffer + i*2N.
-u64* run_fold(Workspace& W, u64* X, u64* Y, int np, int num_cts, int top, int d_begin, int d_end) {
+u64* run_fold(Workspace& W, const FoldOpts& o, u64* X, u64* Y, int np, int num_cts, int top, int d_begin, int d_end) {
   const Params& p = *W.P;
   DeviceState& D = *W.D;
   hipStream_t s = W.stream;
@@ -1396,16 +1392,13 @@ u64* run_fold(Workspace& W, u64* X, u64* Y, int np, int num_cts, int top, int d_
   // levels [d_begin, d_end) of the tree (default: all)
   if (d_end < 0) d_end = further;
   int cur = num_cts >> d_begin;
-  // the workspace's threshold (read when it was created: the digit staging of the unfused levels is sized from it), lowered -- never
-  // raised -- by the run-time switch fused_min_pairs_cap (in-process A/B)
-  const long fused_min = std::min(W.fused_min_pairs, tunable("fused_min_pairs_cap", 1L << 62));
   for (int d = d_begin; d < d_end; d++) {
     const int half = cur / 2;
     // enough independent pairs to fill the chip: one fused workgroup per pair; otherwise (tree tail)
     // the three-kernel form, which parallelises over digits
     if (W.zero_shortcuts && !fused_fold_supported(p))
       throw ArgError("sparse buckets need gadget parameters the fused fold supports (3 <= t_gsw <= 32)");
-    if (W.zero_shortcuts || ((long)np * half >= fused_min && fused_fold_supported(p))) {
+    if (W.zero_shortcuts || ((long)np * half >= o.fused_min_pairs && fused_fold_supported(p))) {
       FoldDesc fd{};
       fd.zero_shortcuts = W.zero_shortcuts ? 1 : 0;
       fd.mats_w = W.mats_w_ready ? W.fold_mats_w.p + (size_t)(top_idx - d) * 2 * 2 * two_t * 2 * POLY_LEN : nullptr;
@@ -1418,14 +1411,14 @@ u64* run_fold(Workspace& W, u64* X, u64* Y, int np, int num_cts, int top, int d_
       fd.t = (int)p.t_gsw;
       fd.bits = (int)p.bits_per(p.t_gsw);
       // digits kd with kd * bits >= modulus_log2 are zero for coefficients below Q (t_gsw = 8: 7 live 8-bit digits of 56 bits)
-      fd.t_live = W.fold_inputs_below_q && tunable("fold_skip_dead_digits", 1)
+      fd.t_live = o.inputs_below_q && tunable("fold_skip_dead_digits", 1)
                       ? (int)std::min<size_t>(p.t_gsw, (p.modulus_log2 + fd.bits - 1) / fd.bits) : fd.t;
       launch_fold_fused(D.T, fd, s);
       std::swap(X, Y);
       cur = half;
       continue;
     }
-    if (W.delta_tail) {
+    if (o.delta_tail) {
       // tree tail in the same delta form as k_fold_fused (half the digit transforms, C only), digit-parallel
       FwdDesc f{};
       f.src = X;
@@ -1698,7 +1691,7 @@ static void fold_local_planes(Workspace& W, const u32* chunk, int G, size_t pg0,
     inv.premod = 1;
     launch_ntt_inv(D.T, inv, s);
   }
-  u64* res = run_fold_canonical(W, W.foldX.p, W.foldY.p, np, npl, (int)p.db_dim_2 - 1);
+  u64* res = run_fold(W, query_fold_opts(W, true), W.foldX.p, W.foldY.p, np, npl, (int)p.db_dim_2 - 1);
   HIP_CHECK(hipMemcpyAsync(W.final_cts.p + pg0 * 2 * POLY_LEN, res, (size_t)np * 2 * POLY_LEN * sizeof(u64), hipMemcpyDeviceToDevice, s));
 }
 
@@ -1746,7 +1739,7 @@ void run_finish_gathered(Workspace& W, const sp_pp& pp, const u64* gathered, int
                                ctw * 8, (size_t)planes, hipMemcpyDeviceToDevice, s));
   int lg = 0;
   while ((1 << lg) < G) lg++;
-  u64* res = run_fold(W, W.foldX.p, W.foldY.p, planes, G, lg - 1);
+  u64* res = run_fold(W, query_fold_opts(W, false), W.foldX.p, W.foldY.p, planes, G, lg - 1);
   HIP_CHECK(hipMemcpyAsync(W.final_cts.p, res, (size_t)planes * ctw * sizeof(u64), hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipEventRecord(W.ev[3], s));
   run_pack(W, pp);

@@ -207,19 +207,29 @@ struct sp_db {
   spiral::ColMap colmap() const { return spiral::ColMap{col_g, col_G, np_local * col_G}; }
   spiral::DevBuf<spiral::u64> words;  // [plane][z][j_local][ii] (or the PACKED unit stream)
   // digit-planar copy of a PACKED database for the 9 .. 16-query pass (sweep_planar.hpp): built from `words` by
-  // sp_db_prepare_batch or by the first such group when the device has the room; bulk writers of `words` invalidate it AFTER their
-  // write, under `mu` (a build between an early invalidation and the end of the write would stay valid and stale),
-  // sp_db_update_item patches its 8 entries per (plane, z) in place.  planar_state: 0 = not built, 1 = valid, -1 = the shape has
-  // no planar form (never tried again), -2 = no room when last tried (tried again by the next group / prepare call).  The memory is
-  // released when the switch `batch_planar` is off, when the copy is invalidated, and when a batched call runs out of memory.
-  spiral::DevBuf<spiral::u64> planar;
+  // sp_db_prepare_batch or by the first such group when the device has the room.  A pass PINS it: ensure_planar hands out the
+  // shared_ptr under `mu` (null: use the PACKED kernels), and the caller keeps it until the pass's stream has been synchronised;
+  // drop_planar only lets go of the handle's reference, the memory goes back when the last pin is released.  Bulk writers of
+  // `words` invalidate it AFTER their write, under `mu` (WriteScope); sp_db_update_item patches its 8 entries per (plane, z) of
+  // the current copy in place.  planar_state: 0 = not built, 1 = valid, -1 = the shape has no planar form (never tried again),
+  // -2 = no room when last tried (tried again by the next group / prepare call).  The handle lets go of the copy when the switch
+  // `batch_planar` is off, when the copy is invalidated, and when a batched call runs out of memory.
+  std::shared_ptr<spiral::DevBuf<spiral::u64>> planar;
   int planar_state = 0;
-  const unsigned char* ensure_planar(hipStream_t s);   // capi.cpp; nullptr: use the PACKED kernels
+  std::shared_ptr<const spiral::DevBuf<spiral::u64>> ensure_planar(hipStream_t s);   // capi.cpp
   void drop_planar() {                                  // caller holds mu
     if (planar_state != -1) planar_state = 0;
-    planar.release();
+    planar.reset();
   }
   std::mutex mu;
+  // a bulk write of `words`: holds `mu` and, on every path out (after the last write has completed), drops the planar copy
+  // before unlocking (a build between an early invalidation and the end of the write would stay valid and stale)
+  struct WriteScope {
+    sp_db& d;
+    std::lock_guard<std::mutex> lk;
+    explicit WriteScope(sp_db& db) : d(db), lk(db.mu) {}
+    ~WriteScope() { d.drop_planar(); }
+  };
   // ---- sparse bucket (sp_db_create_sparse; lib/server/src/db/sparse_db.rs:5-48): only present items are stored
   bool sparse = false;
   std::unordered_map<size_t, size_t> slot_of;  // item index -> slot (db_idx_to_vec_idx)
@@ -237,7 +247,8 @@ struct sp_db {
     std::shared_ptr<spiral::DeviceState::PrunedPlan> plan;
   };
   std::shared_ptr<const SparseIndex> sparse_index;
-  spiral::DevBuf<uint8_t> staging;             // one item's bytes (sp_db_update_item), reused
-  spiral::DevBuf<spiral::u64> load_stage;              // sp_db_load_plane's upload window, kept for the handle's life (switch db_stage_keep; capi.cpp)
+  // the handle's one upload buffer (sp_db_load_plane, sp_db_load_items, sp_db_update_item; used under `mu`), grown and kept for
+  // the handle's life: never freed and allocated again between kernels (profiles/r06_stale_staging.md)
+  spiral::DevBuf<uint8_t> upload;
   std::shared_ptr<const SparseIndex> ensure_sparse_index();  // capi.cpp
 };

@@ -226,6 +226,21 @@ def test_host_threads_through_the_c_abi(emulated, tmp_path, oracle_mod):
     assert r.returncode == 0 and "all equal to the oracle's" in r.stdout, (r.stdout[-1500:], r.stderr[-4000:])
 
 
+def test_batched_pass_pins_the_planar_copy(emulated):
+    """One thread answers lists of eleven queries over a PACKED database's digit-planar copy while another switches batch_planar off
+    and on and calls sp_db_prepare_batch (the copy is dropped and built again): every response == oracle, and -- AddressSanitizer
+    build where there is one -- no heap error.  A pass that does not hold its copy reads one freed or rebuilt under it
+    (tests/_emu_planar_race.py)."""
+    asan = bool(emu_build.ASAN_RUNTIME)
+    lib = emu_build.build(asan=True) if asan else emulated
+    env = dict(os.environ, SPIRAL_HIP_LIB=lib)
+    if asan:
+        env.update(LD_PRELOAD=emu_build.ASAN_RUNTIME, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0:halt_on_error=1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_emu_planar_race.py")], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=1500)
+    assert r.returncode == 0 and "planar-race-ok" in r.stdout, (r.stdout[-1500:], r.stderr[-6000:])
+
+
 def test_bench_and_smoke_refuse_the_emulated_library(emulated):
     env = dict(os.environ, SPIRAL_HIP_LIB=emulated)
     r = subprocess.run([sys.executable, "-c", "import __graft_entry__ as g; g.smoke()"], cwd=ROOT, env=env, capture_output=True,
