@@ -3,6 +3,8 @@
 // tests/test_device_bodies_emulated.py.  What it buys: the CPU suite checks the kernels' arithmetic, index patterns, LDS
 // exchanges and wave swaps against the oracle before anything reaches a GPU.  What it cannot do: run the product (the
 // sweep kernels, the kernels' cross-wave reductions and every launch wrapper need gfx950), or say anything about speed.
+// One exception: sparse.hip is compiled in as well, and emu_sweep_sparse launches its k_sweep_sparse through the unchanged
+// launch_sweep_sparse on operands the caller builds (operand ranges no real item or query reaches).
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -13,6 +15,11 @@
 #include "wave_ntt.hpp"
 
 using namespace spiral;
+
+// sparse.hip's launch wrappers report to server.cpp, which this library does not hold
+namespace spiral {
+void launched(u64, const char*) {}
+}  // namespace spiral
 
 namespace {
 struct EmuParams {
@@ -195,6 +202,18 @@ int emu_digits_to_ntt(void* h, const uint64_t* src, int batch, int rdim, int col
     d.src_cols = cols;
     for (int o = 0; o < d.n_out; o++)
       for (int c = 0; c < 2; c++) emu::run_block(256, [&] { ntt_fwd_body(E.T, d, o, c, g_ldsA, g_ldsB); });
+  });
+}
+
+// k_sweep_sparse (sparse.hip) through launch_sweep_sparse: CSR columns col_ptr[num_per + 1] / col_rows / col_slots, slot
+// polynomials polys[slot][plane][z] (lo | hi << 32), expanded ciphertexts v[ct][r][crt][z] with ct = first + step * row;
+// out[plane][r][crt][z][ii]
+int emu_sweep_sparse(void* h, const int* col_ptr, const int* col_rows, const int* col_slots, const uint64_t* polys, int planes,
+                     const uint32_t* v, int first, int step, uint32_t* out, int num_per) {
+  return guarded([&] {
+    const EmuParams& E = *(EmuParams*)h;
+    launch_sweep_sparse(E.T, col_ptr, col_rows, col_slots, polys, planes, v, first, step, out, num_per, nullptr);
+    if (hipDeviceSynchronize() != hipSuccess) throw std::runtime_error("k_sweep_sparse failed");
   });
 }
 

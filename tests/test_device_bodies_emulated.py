@@ -42,12 +42,12 @@ def emu():
     os.makedirs(BUILD_DIR, exist_ok=True)
     so = os.path.join(BUILD_DIR, "libdevice_bodies_emu.so")
     srcs = [os.path.join(EMU_DIR, "device_bodies_emu.cpp"), os.path.join(EMU_DIR, "emu_runtime.cpp"), os.path.join(EMU_DIR, "emu_streams.cpp"),
-            os.path.join(ROOT, "sdk_amd", "csrc", "params.cpp")]
+            os.path.join(ROOT, "sdk_amd", "csrc", "params.cpp"), os.path.join(ROOT, "sdk_amd", "csrc", "sparse.hip")]
     deps = srcs + [os.path.join(EMU_DIR, "hip", "hip_runtime.h"), os.path.join(EMU_DIR, "emu_runtime.hpp")] + [
         os.path.join(ROOT, "sdk_amd", "csrc", f) for f in ("device_common.hpp", "wave_ntt.hpp", "bodies.hpp", "kernels.hpp",
                                                           "params.hpp")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.run([CLANG, "-std=c++17", "-O1", "-fPIC", "-shared", "-pthread", "-I" + EMU_DIR,
+        subprocess.run([CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-pthread", "-I" + EMU_DIR,
                         "-I" + os.path.join(ROOT, "sdk_amd", "csrc"), "-I" + os.path.join(ROOT, "include")] + srcs +
                        ["-o", so], check=True)
     lib = C.CDLL(so)
@@ -55,7 +55,7 @@ def emu():
     lib.emu_params_new.argtypes = [C.c_char_p]
     lib.emu_last_error.restype = C.c_char_p
     for name in ("emu_params_free", "emu_ntt_block", "emu_ntt_block_m2", "emu_wave_ntt_inv", "emu_wave_ntt_fwd", "emu_from_ntt", "emu_from_sweep",
-                 "emu_digits_to_ntt", "emu_reduce64", "emu_rescale"):
+                 "emu_digits_to_ntt", "emu_reduce64", "emu_rescale", "emu_sweep_sparse"):
         getattr(lib, name).argtypes = None
     h = lib.emu_params_new(json.dumps(FAST).encode())
     assert h, lib.emu_last_error()
@@ -240,3 +240,80 @@ def test_packed_unit_round_trip(emu):                            # the 7-byte PA
     back = np.zeros(256, np.uint64)
     emu.lib.emu_pack_unpack(_p64(words), _p32(unit), _p64(back))
     assert np.array_equal(back, words)
+
+
+def _sweep_sparse(emu, lens, rows, slots, polys, v, first, step):
+    """k_sweep_sparse through launch_sweep_sparse: column ii holds items [sum(lens[:ii]), sum(lens[:ii + 1])) of rows / slots;
+    returns out[plane][r][crt][z][ii] (every word pre-set to a value no reduction yields)"""
+    num_per, planes = len(lens), polys.shape[1]
+    ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    rows_, slots_ = np.ascontiguousarray(rows, np.int32), np.ascontiguousarray(slots, np.int32)
+    out = np.full((planes, 2, 2, N, num_per), 0xFFFFFFFF, np.uint32)
+    ip = C.POINTER(C.c_int32)
+    emu.call("emu_sweep_sparse", ptr.ctypes.data_as(ip), rows_.ctypes.data_as(ip), slots_.ctypes.data_as(ip), _p64(polys),
+             C.c_int(planes), _p32(v), C.c_int(first), C.c_int(step), _p32(out), C.c_int(num_per))
+    return out
+
+
+def _sweep_sparse_exact(lens, rows, slots, polys, v, first, step):
+    """multiply_reg_by_sparse_database (dot_product.rs:13-220) with exact sums: each product (< 2^56) is split into 32-bit
+    halves whose column sums are exact in u64 (<= 2^32 * items), and the sum is reduced as hi * 2^32 + lo"""
+    planes = polys.shape[1]
+    want = np.zeros((planes, 2, 2, N, len(lens)), np.uint64)
+    lo32, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
+    e0 = 0
+    for ii, n in enumerate(lens):
+        if n:
+            a = v[first + step * np.asarray(rows[e0:e0 + n], np.int64)].astype(np.uint64)     # [item][r][crt][z]
+            for pl in range(planes):
+                w = polys[np.asarray(slots[e0:e0 + n], np.int64), pl]                        # [item][z]
+                for crt, q in enumerate((Q0, Q1)):
+                    b = (w & lo32) if crt == 0 else (w >> sh)
+                    for r in range(2):
+                        prod = a[:, r, crt] * b
+                        s_hi, s_lo = (prod >> sh).sum(axis=0), (prod & lo32).sum(axis=0)
+                        qq = np.uint64(q)
+                        want[pl, r, crt, :, ii] = ((s_hi % qq) * np.uint64((1 << 32) % q) + s_lo % qq) % qq
+        e0 += n
+    return want
+
+
+def test_sparse_sweep_worst_case_operands(emu):
+    """k_sweep_sparse accumulates products < 2^56 in u64 and reduces every 255 items: with every operand at q_c - 1 a column of
+    256 items would wrap without that reduction, and a column of 1024 is where the reference's wrapping u64 sums go wrong
+    (include/spiral_hip.h: exact sums mod q).  Columns of 0, 1, 254, 255, 256, 510 and 1024 items, two planes, the production
+    (first, step) = (0, 2)."""
+    lens = [1, 254, 255, 256, 510, 1024, 0]
+    total, n_rows, n_slots, planes = sum(lens), 40, 5, 2
+    rows = np.arange(total) % n_rows
+    slots = (np.arange(total) * 3) % n_slots
+    polys = np.full((n_slots, planes, N), (Q1 - 1) << 32 | (Q0 - 1), np.uint64)
+    v = np.zeros((2 * n_rows, 2, 2, N), np.uint32)
+    v[:, :, 0], v[:, :, 1] = Q0 - 1, Q1 - 1
+    out = _sweep_sparse(emu, lens, rows, slots, polys, v, 0, 2)
+    for ii, n in enumerate(lens):
+        for crt, q in enumerate((Q0, Q1)):
+            exact = n * (q - 1) ** 2 % q                             # Python ints
+            assert np.all(out[:, :, crt, :, ii] == exact), (n, crt)
+            if n == 1024:
+                assert (n * (q - 1) ** 2 % (1 << 64)) % q != exact   # the wrapping u64 sum would be wrong here
+    assert np.array_equal(out.astype(np.uint64), _sweep_sparse_exact(lens, rows, slots, polys, v, 0, 2))
+
+
+@pytest.mark.parametrize("first,step", [(0, 2), (1, 1)])
+def test_sparse_sweep_random_operands(emu, first, step):
+    """random residues, random rows and slots (several items of a column may share a slot), empty columns between full ones"""
+    rng = np.random.default_rng(101 + first)
+    lens = [0, 3, 255, 0, 256, 300, 511]
+    total, n_rows, n_slots, planes = sum(lens), 64, 37, 2
+    rows = rng.integers(0, n_rows, total)
+    slots = rng.integers(0, n_slots, total)
+    polys = rng.integers(0, Q0, (n_slots, planes, N), dtype=np.uint64) | (rng.integers(0, Q1, (n_slots, planes, N), dtype=np.uint64) << np.uint64(32))
+    polys[0] = (Q1 - 1) << 32 | (Q0 - 1)
+    v = np.zeros((first + step * n_rows, 2, 2, N), np.uint32)
+    v[:, :, 0] = rng.integers(0, Q0, v[:, :, 0].shape, dtype=np.uint64)
+    v[:, :, 1] = rng.integers(0, Q1, v[:, :, 1].shape, dtype=np.uint64)
+    out = _sweep_sparse(emu, lens, rows, slots, polys, v, first, step)
+    want = _sweep_sparse_exact(lens, rows, slots, polys, v, first, step)
+    assert np.array_equal(out.astype(np.uint64), want)
+    assert not np.any(out[..., [0, 3]])                               # absent columns are zeros (the fold's shortcuts rely on it)

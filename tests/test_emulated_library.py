@@ -3,8 +3,8 @@
 tests/emu/ builds sdk_amd/csrc unchanged for the host (a stand-in <hip/hip_runtime.h>: workgroups as fibers, barriers and
 wave exchanges as scheduling points, device memory = host memory, gfx950 builtins restated in C) into
 tests/emu/_build/libspiral_emu.so with the C ABI of libspiral_hip.so.  The tests below run a subset of the `-m gpu` parity
-tests (tests/test_gpu_parity.py, byte comparisons with the oracle) against that build in a child process
-(SPIRAL_HIP_LIB selects the library file), once more under AddressSanitizer, where every device buffer is a heap block with
+tests (tests/test_gpu_parity.py and tests/test_sparse_bucket.py, byte comparisons with the oracle) against that build in a
+child process (SPIRAL_HIP_LIB selects the library file), once more under AddressSanitizer, where every device buffer is a heap block with
 red zones: an out-of-bounds read or write of any kernel on these shapes is an error, which no GPU run can show.
 
 This is test infrastructure.  It is not a fallback: sdk_amd never builds or loads it, bench.py and smoke() refuse it, and the
@@ -45,12 +45,19 @@ STREAM_SUBSET = ("(test_process_query_bytes_and_decode and fast56) or (test_ring
                  "or (test_expansion_variants_response_parity and 0-split) or (test_process_query_batch and narrow-3)")
 ASAN_SUBSET = ("(test_process_query_bytes_and_decode and (fast-0 or fast56 or nu2_0)) or test_fold_pack_encode or (test_multiply and not 1024 and not 2048) "
                "or (test_wave_fold_kernel_gadget_widths and (0 or 4))")
+# sparse buckets (tests/test_sparse_bucket.py): a column of 256 items (one reduction of the sweep's u64 sums), the right half of
+# 16 columns empty (shortcuts at every fold level), zero and short items (one plane shortcut while the others are not)
+SPARSE_SUBSET = ("(test_sparse_deep_columns and nu1_8) or (test_sparse_empty_column_patterns and right_half_empty and inst1) "
+                 "or (test_sparse_zero_and_short_items and inst1)")
+SPARSE_LONG_SUBSET = ("test_sparse_empty_column_patterns or test_sparse_zero_and_short_items or test_sparse_pruned_expansion_row_sets "
+                      "or test_sparse_index_rebuilds_and_snapshots or test_sparse_bucket_query_lists")
+ASAN_SPARSE_SUBSET = "test_sparse_empty_column_patterns and left_half_empty and inst2"
 
 
-def _run(lib, expr, extra_env=None, timeout=1500, at_least=5):
+def _run(lib, expr, extra_env=None, timeout=1500, at_least=5, test_file="test_gpu_parity.py"):
     env = dict(os.environ, SPIRAL_HIP_LIB=lib)
     env.update(extra_env or {})
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-q", "-x",
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", test_file), "-m", "gpu", "-q", "-x",
                         "-p", "no:cacheprovider", "-k", expr], cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     tail = (r.stdout + r.stderr)[-3000:]
     assert r.returncode == 0, tail
@@ -73,6 +80,19 @@ def test_parity_subset_on_the_emulated_device(emulated):
     the one under which a missing wait between a plane's sweep and its fold fails -- see
     test_host_pipeline_survives_adversarial_stream_orders.)"""
     assert _run(emulated, SUBSET, {"SPIRAL_EMU_STREAMS": "starve:1"}) >= 38
+
+
+def test_sparse_bucket_subset_on_the_emulated_device(emulated):
+    """lib/server's sparse caller (sp_db_create_sparse + sp_db_update_item: k_sparse_item_encode, k_sweep_sparse, the pruned
+    expansion, the fused fold with its all-zero shortcuts) against the oracle, with the streams in `starve:1` order"""
+    assert _run(emulated, SPARSE_SUBSET, {"SPIRAL_EMU_STREAMS": "starve:1"}, at_least=3, test_file="test_sparse_bucket.py") >= 3
+
+
+@long_only
+def test_sparse_bucket_cases_on_the_emulated_device(emulated):
+    """the rest of the small sparse cases: every empty-column pattern, the row sets of the pruned expansion, index rebuilds and
+    snapshots, lists with 1, 2 and 4 queries in flight"""
+    assert _run(emulated, SPARSE_LONG_SUBSET, {"SPIRAL_EMU_STREAMS": "random:5"}, at_least=30, test_file="test_sparse_bucket.py") >= 30
 
 
 @long_only
@@ -112,6 +132,7 @@ def test_kernels_stay_inside_their_buffers(emulated):
            "ASAN_OPTIONS": "detect_leaks=0:detect_stack_use_after_return=0:halt_on_error=1:log_path=" + log}
     try:
         _run(so, ASAN_SUBSET, env)
+        _run(so, ASAN_SPARSE_SUBSET, env, at_least=1, test_file="test_sparse_bucket.py")
     finally:
         reports = [f for f in os.listdir(emu_build.BUILD) if f.startswith("asan_report")]
         if reports:
