@@ -196,6 +196,16 @@ int sp_query_sweep_scatter(sp_query_t*, const sp_db_t*, int G);
  * each plane can be reduce-scattered on its own, overlapping the exchange of plane p with the sweep of plane p+1;
  * the concatenation of the received chunks is the [plane][r][crt][z][ii / G] buffer sp_query_fold_local takes. */
 int sp_query_sweep_scatter_plane(sp_query_t*, const sp_db_t*, int G, int plane);
+/* ALL planes for a GROUP of 1 .. 8 queries begun for this row shard (sp_query_begin_for_db) with ONE pass over the shard's
+ * rows: afterwards every sp_query_partial_ptr(qs[i]) holds, word for word, what `planes` calls of
+ * sp_query_sweep_scatter_plane(qs[i], shard, G, p) would have left, and sp_query_fold_local / sp_query_finish_gathered take
+ * over unchanged.  The pass runs on qs[0]'s stream, ordered after every query's expansion; each query's own stream is
+ * ordered after the pass.  From 4 queries on PACKED shards with whole 32-row blocks (G = 2, 4, 8) it is one launch of the
+ * matrix-core kernel in its scatter form (path bits scatter_out, sweep_batch, sweep_batch_mfma, sweep_batch_scatter); every
+ * other group or shape is swept per query inside the same call (the bit sweep_batch_scatter stays clear).  SP_E_ARG, nothing
+ * enqueued: column-sharded or unsharded handle with G > 1, G != the handle's shard count, a query begun for other
+ * params / rows or not in the 'begun' state. */
+int sp_query_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* shard, int G);
 int sp_query_fold_local(sp_query_t*, const void* reduced_chunk_dev, int G);
 /* The local fold one plane at a time on the query's SECOND stream (sp_query_stream2), planes in order: plane p may
  * be folded as soon as it has been swept and its reduced chunk ([r][crt][z][ii / G]) is complete — the caller orders
@@ -271,6 +281,18 @@ int sp_process_query_sharded(sp_comm_t*, const sp_params_t*, const sp_pp_t*, con
 int sp_process_queries_sharded(sp_comm_t*, const sp_params_t*, const sp_pp_t* const* pps, const uint8_t* const* queries,
                                const size_t* query_lens, int n, const sp_db_t* shard, uint8_t* out, size_t out_stride,
                                size_t* out_len);
+/* The same list with the DATABASE PASS SHARED inside groups of up to 8 queries: per group, `B` pruned expansions, one
+ * sp_query_sweep_scatter_group over the rank's shard, then per query (in list order) `planes` reduce_scatter_u32 into that
+ * query's region of the rank's receive buffer, and per query (in list order) sp_query_fold_local, all_gather_u64 and, on rank
+ * 0, sp_query_finish_gathered.  group: 1 .. 8, or 0 = the library's choice (8 where the scatter-form pass applies to the
+ * shard, else the per-query flow of sp_process_queries_sharded).  The sequence of collectives is a function of (n, group,
+ * params, shard shape) alone, so every rank issues the same one.  Every query's length is checked before anything is begun:
+ * a bad list enters no collective.  Same outputs and the same bytes as sp_process_queries_sharded. */
+int sp_process_queries_sharded_batched(sp_comm_t*, const sp_params_t*, const sp_pp_t* const* pps, const uint8_t* const* queries,
+                                       const size_t* query_lens, int n, const sp_db_t* shard, int group, uint8_t* out,
+                                       size_t out_stride, size_t* out_len);
+/* sp_comm_reserve plus the receive / gather buffers and events of a group of `group` (1 .. 8; 0 = 8) queries. */
+int sp_comm_reserve_batch(sp_comm_t*, const sp_params_t* params, int group);
 /* Allocates the communicator's exchange buffers and events for `params` now, so that no sharded query allocates
  * anything (otherwise the first query with new params does).  Not a collective. */
 int sp_comm_reserve(sp_comm_t*, const sp_params_t* params);
@@ -326,6 +348,11 @@ int sp_bench_sweep_ex(sp_query_t* q, const sp_db_t* db, int iters, int per_plane
  * the matrix cores from 4 queries, k_sweep_packed_batch below; one launch over all planes); returns average
  * milliseconds per PASS.  The queries' partial buffers hold the pass's outputs afterwards. */
 int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, int iters, float* ms_per_pass);
+/* ... and for the pass of sp_query_sweep_scatter_group over a row shard (queries begun for it): layout 1 = the scatter-form
+ * pass as the group call launches it, 0 = the existing one-tile pass over the same rows writing the plain [z][ii] layout
+ * (comparison only: what the interleaved stores cost).  SP_E_ARG where the group call would sweep per query. */
+int sp_bench_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* shard, int G, int layout, int iters,
+                                 float* ms_per_pass);
 
 /* Diagnostics: where workgroups land.  `blocks` 64-thread workgroups are launched on a stream whose CU mask has bits
  * [bit_lo, bit_hi) set (no mask when bit_hi <= bit_lo); out2[2b] = HW_REG_XCC_ID, out2[2b+1] = HW_REG_HW_ID of

@@ -100,6 +100,7 @@ pub mod sys {
         // ---- the same call split around the exchange step (multi-GPU driven by the caller)
         pub fn sp_query_sweep_scatter(q: *mut sp_query_t, db: *const sp_db_t, g: c_int) -> c_int;
         pub fn sp_query_sweep_scatter_plane(q: *mut sp_query_t, db: *const sp_db_t, g: c_int, plane: c_int) -> c_int;
+        pub fn sp_query_sweep_scatter_group(qs: *const *mut sp_query_t, batch: c_int, shard: *const sp_db_t, g: c_int) -> c_int;
         pub fn sp_query_fold_local(q: *mut sp_query_t, reduced_chunk_dev: *const c_void, g: c_int) -> c_int;
         pub fn sp_query_fold_local_plane(q: *mut sp_query_t, reduced_plane_chunk_dev: *const c_void, g: c_int, plane: c_int) -> c_int;
         pub fn sp_query_fold_local_join(q: *mut sp_query_t) -> c_int;
@@ -135,6 +136,11 @@ pub mod sys {
                                           query_lens: *const usize, n: c_int, shard: *const sp_db_t, out: *mut u8, out_stride: usize,
                                           out_len: *mut usize) -> c_int;
         pub fn sp_comm_reserve(c: *mut sp_comm_t, p: *const sp_params_t) -> c_int;
+        pub fn sp_comm_reserve_batch(c: *mut sp_comm_t, p: *const sp_params_t, group: c_int) -> c_int;
+        pub fn sp_process_queries_sharded_batched(c: *mut sp_comm_t, p: *const sp_params_t, pps: *const *const sp_pp_t,
+                                                  queries: *const *const u8, query_lens: *const usize, n: c_int,
+                                                  shard: *const sp_db_t, group: c_int, out: *mut u8, out_stride: usize,
+                                                  out_len: *mut usize) -> c_int;
         pub fn sp_comm_timings(c: *const sp_comm_t, ms3: *mut f32) -> c_int;
         pub fn sp_comm_describe(c: *const sp_comm_t, buf: *mut c_char, cap: usize) -> c_int;
         // ---- request layer: lib/server/src/bin/server.rs ServerState, /setup, /private-read (no HTTP)
@@ -157,6 +163,8 @@ pub mod sys {
                                  ms_per_launch: *mut f32) -> c_int;
         pub fn sp_bench_sweep_batch(qs: *const *mut sp_query_t, batch: c_int, db: *const sp_db_t, iters: c_int,
                                     ms_per_pass: *mut f32) -> c_int;
+        pub fn sp_bench_sweep_scatter_group(qs: *const *mut sp_query_t, batch: c_int, shard: *const sp_db_t, g: c_int,
+                                            layout: c_int, iters: c_int, ms_per_pass: *mut f32) -> c_int;
         pub fn sp_debug_cu_probe(bit_lo: c_int, bit_hi: c_int, blocks: c_int, out2: *mut u32) -> c_int;
         pub fn sp_debug_resident_check(params: *const sp_params_t, pp: *const sp_pp_t, out: *mut u64, cap: c_int) -> c_int;
         pub fn sp_debug_chacha20_u64(seed: *const u8, out: *mut u64, count: usize) -> c_int;

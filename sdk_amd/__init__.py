@@ -10,6 +10,7 @@ from .spiral import (
     add_into,
     scalar_multiply,
     bench_sweep_batch,  # noqa: F401
+    bench_sweep_scatter_group,  # noqa: F401
     Database,
     Params,
     PolyMatrixNTT,

@@ -306,6 +306,18 @@ int sp_debug_set(const char* name, long value) {
 // internal hooks for comm.cpp (not declared in the public header)
 static thread_local int g_shard_split_hint = 1;   // 0 while a list of sharded queries is being enqueued
 extern "C" void sp_shard_split_hint_(int on) { g_shard_split_hint = on; }
+// group = 0 of sp_process_queries_sharded_batched: 8 where a group of 8 takes the scatter-form pass on this shard and the shard
+// count is one where the batched list measured faster than the pipelined one (switch batch_scatter_max_g; profiles/sharded_batch_pass.md),
+// else 1 = the per-query flow.  Depends on the shard's shape and the switches only: the same answer on every rank.
+extern "C" int sp_scatter_group_choice_(const sp_db_t* db, int G) {
+  if (!db || !db->packed || db->col_G != 1 || db->sparse || db->num_shards != G) return 1;
+  SweepBatchDesc d{};
+  d.batch = SWEEP_BATCH_MAX;
+  d.num_per = db->np_local;
+  d.nj = db->nj;
+  tunables_new_call();
+  return sweep_batch_scatter_ok(d, G) && G <= (int)tunable("batch_scatter_max_g", BATCH_SCATTER_MAX_G_DEFAULT) ? SWEEP_BATCH_MAX : 1;
+}
 void sp_set_last_error_(const char* msg) { g_last_error = msg ? msg : ""; }
 void sp_note_path_(uint64_t bits) { note_path(bits); }
 
@@ -317,7 +329,7 @@ const char* sp_path_name(int bit) {
                                 "rccl_in_library", "fold_wave", "cu_split_overlap", "expand_split", "pipe_class_split",
                                 "sweep_batch_mfma", "custom_transport", "from_sweep_wave",
                                 "fold_tail_batched", "sweep_ring", "sweep_batch_mfma_two_tiles", "fold_wave8", "sweep_batch_planar",
-                                "expand_group", "expand_wave"};
+                                "expand_group", "expand_wave", "sweep_batch_scatter"};
   return bit >= 0 && bit < (int)(sizeof(names) / sizeof(names[0])) ? names[bit] : nullptr;
 }
 
@@ -898,6 +910,77 @@ int sp_query_sweep_scatter_plane(sp_query_t* q, const sp_db_t* db, int G, int pl
   });
 }
 
+// One pass over the row shard for a whole group (the stage between sp_query_begin_for_db and sp_query_fold_local of the batched
+// sharded list, comm.cpp).  Checks first, nothing enqueued on an error.
+static void scatter_group_check(sp_query_t* const* qs, int batch, const sp_db_t* db, int G) {
+  need(qs && db, "null argument");
+  need(batch >= 1 && batch <= SWEEP_BATCH_MAX, "sp_query_sweep_scatter_group: 1 .. 8 queries per pass");
+  const Params& p = db->params->p;
+  need(db->col_G == 1 && !db->sparse, "sweep_scatter works on row shards");
+  need(G >= 1 && (G & (G - 1)) == 0 && (size_t)G <= p.num_per() && db->num_shards == G && G <= SP_MAX_ROW_SHARDS,
+       "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS) and equal to the db's num_shards");
+  for (int i = 0; i < batch; i++) {
+    need(qs[i] && qs[i]->ws, "null query");
+    need(qs[i]->params == db->params, "db was created for different params");
+    need(qs[i]->rows_nj == 0 || (db->j0 == qs[i]->rows_j0 && db->nj == qs[i]->rows_nj),
+         "the query was expanded for another row shard (sp_query_begin_for_db)");
+    for (int k = 0; k < i; k++) need(qs[k] != qs[i], "sp_query_sweep_scatter_group: the same query twice");
+  }
+  check_device(db->device);
+}
+// the group's pass in the reduce-scatter layout on the first query's stream (prepared descriptor); false: this group or shape is
+// not the matrix-core pass's -- the caller sweeps per query
+static bool scatter_group_desc(sp_query_t* const* qs, int batch, const sp_db_t* db, int G, SweepBatchDesc& d) {
+  for (int i = 0; i < batch; i++) qs[i]->ws->ensure_sweep();
+  if (!db->packed || G < 2) return false;
+  PlanarPin none;
+  d = group_pass(*db, qs, batch, false, none);
+  return d.rq != nullptr && sweep_batch_scatter_ok(d, G);
+}
+
+int sp_query_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* db, int G) {
+  return guarded([&] {
+    scatter_group_check(qs, batch, db, G);
+    for (int i = 0; i < batch; i++)
+      need(qs[i]->state == 1 && qs[i]->next_plane == 0, "sp_query_sweep_scatter_group: every query must be in 'begun' state, no plane swept");
+    const size_t planes = db->params->p.planes();
+    SweepBatchDesc d{};
+    if (scatter_group_desc(qs, batch, db, G, d)) {
+      // ordered after every query's expansion (ev[1], recorded by sp_query_begin_for_db on the query's stream; the operand of
+      // the pass, qv, is written on that stream also when the odd subtree was split off) ...
+      Workspace& W0 = *qs[0]->ws;
+      for (int i = 1; i < batch; i++) HIP_CHECK(hipStreamWaitEvent(W0.stream, qs[i]->ws->ev[1], 0));
+      sweep_batch_prepare(W0.D->T, d, W0.stream);
+      launch_sweep_batch_scatter(W0.D->T, d, G, W0.stream);
+      HIP_CHECK(hipEventRecord(W0.ev[2], W0.stream));
+      // ... and every query's own stream after the pass
+      for (int i = 1; i < batch; i++) {
+        Workspace& W = *qs[i]->ws;
+        HIP_CHECK(hipStreamWaitEvent(W.stream, W0.ev[2], 0));
+        HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
+      }
+    } else {
+      // groups of 1 .. 3, rows that are not whole 32-row blocks, 8-byte databases, batch_mfma = 0: the per-query scatter sweep
+      for (int i = 0; i < batch; i++) {
+        Workspace& W = *qs[i]->ws;
+        W.out_G = G;
+        try {
+          for (size_t pl = 0; pl < planes; pl++) launch_plane_sweep(W, *db, pl);
+        } catch (...) {
+          W.out_G = 1;
+          throw;
+        }
+        W.out_G = 1;
+        HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
+      }
+    }
+    for (int i = 0; i < batch; i++) {
+      qs[i]->next_plane = (int)planes;
+      qs[i]->state = 2;
+    }
+  });
+}
+
 int sp_query_fold_local(sp_query_t* q, const void* reduced_chunk, int G) {
   return guarded([&] {
     need(q && reduced_chunk, "null argument");
@@ -1335,6 +1418,41 @@ int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, in
     auto pass = [&] {
       sweep_batch_prepare(W0.D->T, d, W0.stream);
       launch_sweep_batch(W0.D->T, d, W0.stream);
+    };
+    pass();  // warm
+    HIP_CHECK(hipEventRecord(ev.a, W0.stream));
+    for (int i = 0; i < iters; i++) pass();
+    HIP_CHECK(hipEventRecord(ev.b, W0.stream));
+    HIP_CHECK(hipStreamSynchronize(W0.stream));
+    float t = 0;
+    HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+    *ms_per_pass = t / (float)iters;
+  });
+}
+
+int sp_bench_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* db, int G, int layout, int iters, float* ms_per_pass) {
+  return guarded([&] {
+    need(ms_per_pass && iters > 0 && (layout == 0 || layout == 1), "bad argument");
+    scatter_group_check(qs, batch, db, G);
+    for (int i = 0; i < batch; i++) {
+      need(qs[i]->state >= 1, "query not begun");
+      HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream));   // expansions done: the pass is timed alone
+      HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream2));
+    }
+    SweepBatchDesc d{};
+    need(scatter_group_desc(qs, batch, db, G, d), "this group / shard does not take the scatter-form pass (sp_query_sweep_scatter_group would sweep per query)");
+    Workspace& W0 = *qs[0]->ws;
+    struct Drain {
+      hipStream_t s;
+      ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{W0.stream};
+    TimingEvents ev;
+    auto pass = [&] {
+      sweep_batch_prepare(W0.D->T, d, W0.stream);
+      if (layout == 1)
+        launch_sweep_batch_scatter(W0.D->T, d, G, W0.stream);
+      else
+        launch_sweep_batch(W0.D->T, d, W0.stream);   // the same rows, plain [z][ii] output: the scatter form's lower bound
     };
     pass();  // warm
     HIP_CHECK(hipEventRecord(ev.a, W0.stream));

@@ -21,6 +21,7 @@
 #include <rccl/rccl.h>
 
 #include <cstdio>
+#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -31,6 +32,7 @@
 extern "C" void sp_set_last_error_(const char* msg);  // capi.cpp
 extern "C" void sp_note_path_(uint64_t bits);         // capi.cpp
 extern "C" void sp_shard_split_hint_(int on);         // capi.cpp: may the next sp_query_begin_for_db of this thread split the expansion?
+extern "C" int sp_scatter_group_choice_(const sp_db_t* shard, int G);   // capi.cpp: group size of a batched sharded list left to the library
 
 namespace {
 
@@ -67,6 +69,10 @@ struct sp_comm {
   size_t mine_bytes = 0;
   void* gathered = nullptr;       // [g][plane][2][N] u64
   size_t gathered_bytes = 0;
+  // batched list (sp_process_queries_sharded_batched): per query of a group, its exchanges are done / its all-gather is done
+  std::vector<hipEvent_t> ev_bx, ev_bg;
+  int last_group = 0;             // group size of the last list call (0: none yet; 1: the per-query flow), and its collectives
+  size_t last_reduce_scatters = 0, last_all_gathers = 0;
   float ms[3] = {0, 0, 0};
   std::mutex mu;                  // one sharded query at a time per communicator (collective order must match on all ranks)
 
@@ -95,8 +101,9 @@ struct sp_comm {
   ~sp_comm() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (nccl) (void)ncclCommDestroy(nccl);
-    for (auto e : ev_plane)
-      if (e) (void)hipEventDestroy(e);
+    for (auto* v : {&ev_plane, &ev_bx, &ev_bg})
+      for (auto e : *v)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {ev_x, ev_f, ev_g, ev_t[0], ev_t[1], ev_t[2], ev_rs})
       if (e) (void)hipEventDestroy(e);
     if (mine) (void)hipFree(mine);
@@ -197,10 +204,12 @@ int sp_comm_describe(const sp_comm_t* c, char* buf, size_t cap) {
                          "\"planes\": %zu, \"reduce_scatter_u32\": {\"per_plane_send_bytes\": %zu, \"per_plane_recv_bytes\": %zu, "
                          "\"per_query_link_bytes_ring\": %zu}, \"all_gather_u64\": {\"send_bytes\": %zu, \"recv_bytes\": %zu}, "
                          "\"last_query_ms\": {\"sweeps_with_overlapped_exchange\": %.4f, \"tail_fold_gather\": %.4f, "
-                         "\"exposed_exchange_after_last_sweep\": %.4f}}",
+                         "\"exposed_exchange_after_last_sweep\": %.4f}, "
+                         "\"last_list\": {\"group\": %d, \"reduce_scatters\": %zu, \"all_gathers\": %zu}}",
                          c->custom ? "custom" : "rccl", ver, c->rank, G, c->device, c->planes_last, c->rs_recv_bytes * (size_t)G,
                          c->rs_recv_bytes, c->planes_last * c->rs_recv_bytes * (size_t)(G - 1), c->ag_send_bytes,
-                         c->ag_send_bytes * (size_t)G, (double)c->ms[0], (double)c->ms[1], (double)c->ms[2]);
+                         c->ag_send_bytes * (size_t)G, (double)c->ms[0], (double)c->ms[1], (double)c->ms[2], c->last_group,
+                         c->last_reduce_scatters, c->last_all_gathers);
   return n > 0 && (size_t)n < cap ? SP_OK : SP_E_ARG;
 }
 
@@ -211,7 +220,7 @@ int sp_comm_timings(const sp_comm_t* c, float* ms3) {
 }
 
 // sizes of the exchange buffers for `h`, allocated now (sp_comm_reserve) or, failing that, by the first sharded query
-static void comm_reserve(sp_comm_t* c, const sp_params_t* h) {
+static void comm_reserve(sp_comm_t* c, const sp_params_t* h, int group = 1) {
   const int G = c->world;
   const size_t planes = (size_t)sp_params_get(h, "instances") * sp_params_get(h, "n") * sp_params_get(h, "n");
   const size_t num_per = (size_t)1 << sp_params_get(h, "db_dim_2");
@@ -219,8 +228,15 @@ static void comm_reserve(sp_comm_t* c, const sp_params_t* h) {
   if (num_per % (size_t)G != 0) throw Fail{SP_E_ARG, "num_per is not a multiple of the number of ranks: the column chunks of the exchange would be ragged"};
   const size_t chunk = 4 * (size_t)sp_params_get(h, "poly_len") * num_per / (size_t)G;   // u32 [r][crt][z][ii / G] of one plane
   const size_t local_words = planes * 2 * (size_t)sp_params_get(h, "poly_len");         // one raw ciphertext per plane
-  c->ensure(c->mine, c->mine_bytes, planes * chunk * sizeof(uint32_t));
-  c->ensure(c->gathered, c->gathered_bytes, (size_t)G * local_words * sizeof(uint64_t));
+  // (a batched list keeps one region per query of a group in each buffer: [query][plane][r][crt][z][ii / G], [query][g][plane][2][N])
+  c->ensure(c->mine, c->mine_bytes, (size_t)group * planes * chunk * sizeof(uint32_t));
+  c->ensure(c->gathered, c->gathered_bytes, (size_t)group * G * local_words * sizeof(uint64_t));
+  for (auto* v : {&c->ev_bx, &c->ev_bg})
+    while (group > 1 && v->size() < (size_t)group) {
+      hipEvent_t e = nullptr;
+      hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+      v->push_back(e);
+    }
   if (c->ev_plane.size() < planes) {
     const size_t old = c->ev_plane.size();
     c->ev_plane.resize(planes, nullptr);
@@ -235,6 +251,15 @@ int sp_comm_reserve(sp_comm_t* c, const sp_params_t* h) {
   }
   std::lock_guard<std::mutex> lk(c->mu);
   return guarded_comm([&] { comm_reserve(c, h); });
+}
+
+int sp_comm_reserve_batch(sp_comm_t* c, const sp_params_t* h, int group) {
+  if (!c || !h || group < 0 || group > 8) {
+    sp_set_last_error_(!c || !h ? "null argument" : "group must be 0 (= 8) or 1 .. 8");
+    return SP_E_ARG;
+  }
+  std::lock_guard<std::mutex> lk(c->mu);
+  return guarded_comm([&] { comm_reserve(c, h, group == 0 ? 8 : group); });
 }
 
 namespace {
@@ -346,14 +371,10 @@ int sp_process_query_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t* 
   return rc;
 }
 
-int sp_process_queries_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t* const* pps, const uint8_t* const* queries,
-                               const size_t* query_lens, int n, const sp_db_t* shard, uint8_t* out, size_t out_stride,
-                               size_t* out_len) {
-  if (!c || !h || !pps || !queries || !query_lens || n < 0 || !shard || !out_len || (c->rank == 0 && n > 0 && !out)) {
-    sp_set_last_error_("null argument");
-    return SP_E_ARG;
-  }
-  std::lock_guard<std::mutex> lk(c->mu);
+// the pipelined list, c->mu held (sp_process_queries_sharded; also the per-query flow of the batched entry point)
+static int queries_sharded_locked(sp_comm_t* c, const sp_params_t* h, const sp_pp_t* const* pps, const uint8_t* const* queries,
+                                  const size_t* query_lens, int n, const sp_db_t* shard, uint8_t* out, size_t out_stride,
+                                  size_t* out_len) {
   ShardedRun cur, nxt;
   int rc = guarded_comm([&] {
     int dev = 0;
@@ -379,6 +400,9 @@ int sp_process_queries_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t
     (void)hipEventElapsedTime(&c->ms[1], c->ev_t[1], c->ev_t[2]);
     if (hipEventElapsedTime(&c->ms[2], c->ev_t[1], c->ev_rs) != hipSuccess || c->ms[2] < 0) c->ms[2] = 0;
     note_transport(c);
+    c->last_group = 1;
+    c->last_reduce_scatters = (size_t)n * c->planes_last;
+    c->last_all_gathers = (size_t)n;
   });
   for (ShardedRun* r : {&cur, &nxt})
     if (r->q) {
@@ -386,6 +410,136 @@ int sp_process_queries_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t
       (void)sp_query_sync(r->q);
       sp_query_free(r->q);
     }
+  return rc;
+}
+
+int sp_process_queries_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t* const* pps, const uint8_t* const* queries,
+                               const size_t* query_lens, int n, const sp_db_t* shard, uint8_t* out, size_t out_stride,
+                               size_t* out_len) {
+  if (!c || !h || !pps || !queries || !query_lens || n < 0 || !shard || !out_len || (c->rank == 0 && n > 0 && !out)) {
+    sp_set_last_error_("null argument");
+    return SP_E_ARG;
+  }
+  std::lock_guard<std::mutex> lk(c->mu);
+  return queries_sharded_locked(c, h, pps, queries, query_lens, n, shard, out, out_stride, out_len);
+}
+
+// ---- the same list with the database pass shared inside groups of up to 8 queries ---------------------------------------------
+// Order of the collectives, a function of (n, group, params) alone -- every rank passes the same list, so every rank issues
+// the same sequence on its exchange stream.  For each group of B = min(group, n - first) queries, in list order:
+//   for i in 0 .. B:  for plane in 0 .. planes:  reduce_scatter_u32(query i's plane region -> region i of the receive buffer)
+//   for i in 0 .. B:  all_gather_u64(query i's local ciphertexts -> region i of the gather buffer)
+// and nothing of group k + 1 before the last all-gather of group k.  Host side per group: B pruned expansions (each on its
+// query's streams), ONE sp_query_sweep_scatter_group, the reduce-scatters (the exchange stream waits for the pass once per
+// query), then per query the local fold on its own stream and its all-gather; group k + 1's expansions are enqueued before the
+// host waits for group k's responses, so they run under group k's exchanges and folds.  Only then rank 0 finishes the
+// queries (the other ranks wait for their streams): the receive and gather regions are free for the next group.
+int sp_process_queries_sharded_batched(sp_comm_t* c, const sp_params_t* h, const sp_pp_t* const* pps, const uint8_t* const* queries,
+                                       const size_t* query_lens, int n, const sp_db_t* shard, int group, uint8_t* out,
+                                       size_t out_stride, size_t* out_len) {
+  if (!c || !h || !pps || !queries || !query_lens || n < 0 || !shard || !out_len || (c->rank == 0 && n > 0 && !out)) {
+    sp_set_last_error_("null argument");
+    return SP_E_ARG;
+  }
+  if (group < 0 || group > 8) {
+    sp_set_last_error_("group must be 0 (the library's choice) or 1 .. 8");
+    return SP_E_ARG;
+  }
+  // every query's length before anything is begun: a bad list must not leave this rank inside a collective the others never enter
+  const size_t qbytes = (size_t)sp_params_get(h, "query_bytes");
+  for (int k = 0; k < n; k++)
+    if (!queries[k] || !pps[k] || query_lens[k] != qbytes) {
+      sp_set_last_error_(("query " + std::to_string(k) + " of the list: expected " + std::to_string(qbytes) + " bytes").c_str());
+      return SP_E_ARG;
+    }
+  std::lock_guard<std::mutex> lk(c->mu);
+  const int G = c->world;
+  if (group == 0) group = sp_scatter_group_choice_(shard, G);   // 8 where the scatter-form pass takes this shard (and pays), else 1
+  if (group == 1 || n == 0) return queries_sharded_locked(c, h, pps, queries, query_lens, n, shard, out, out_stride, out_len);
+  std::vector<ShardedRun> cur, nxt;
+  auto drop = [&](std::vector<ShardedRun>& v) {
+    for (auto& r : v)
+      if (r.q) {
+        (void)sp_query_sync(r.q);
+        sp_query_free(r.q);
+      }
+    v.clear();
+  };
+  auto begin_group = [&](int first, std::vector<ShardedRun>& v) {
+    const int B = std::min(group, n - first);
+    v.assign((size_t)B, ShardedRun{});
+    for (int i = 0; i < B; i++) sharded_begin(c, h, pps[first + i], queries[first + i], query_lens[first + i], shard, v[i], false);
+  };
+  int rc = guarded_comm([&] {
+    int dev = 0;
+    hip_ok(hipGetDevice(&dev), "hipGetDevice");
+    if (dev != c->device) throw Fail{SP_E_ARG, "the communicator was created on another HIP device"};
+    *out_len = 0;
+    comm_reserve(c, h, group);   // no-op after sp_comm_reserve_batch / the first list with these params and this group
+    size_t n_rs = 0, n_ag = 0;
+    begin_group(0, cur);
+    for (int first = 0; first < n; first += group) {
+      const int B = (int)cur.size();
+      const size_t planes = cur[0].planes, local_words = cur[0].local_words;
+      sp_query_t* qs[8];
+      for (int i = 0; i < B; i++) qs[i] = cur[i].q;
+      sp_ok(sp_query_sweep_scatter_group(qs, B, shard, G), "sp_query_sweep_scatter_group");
+      const size_t words = sp_query_partial_words(qs[0]), pw = words / planes, chunk = pw / (size_t)G;
+      if (words % planes != 0 || pw % (size_t)G != 0 || (size_t)B * planes * chunk * sizeof(uint32_t) > c->mine_bytes ||
+          (size_t)B * G * local_words * sizeof(uint64_t) > c->gathered_bytes)
+        throw Fail{SP_E_ARG, "internal: the queries' partial buffers do not match the reserved exchange buffers"};
+      for (int i = 0; i < B; i++) {
+        uint32_t* part = (uint32_t*)sp_query_partial_ptr(qs[i]);
+        if (!part) throw Fail{SP_E_OOM, std::string("partial buffer: ") + sp_last_error()};
+        // query i's stream is ordered after the pass (or carries its own sweeps): the exchange stream waits for it
+        hip_ok(hipEventRecord(c->ev_plane[0], cur[i].main), "hipEventRecord");
+        hip_ok(hipStreamWaitEvent(c->stream, c->ev_plane[0], 0), "hipStreamWaitEvent");
+        uint32_t* mine = (uint32_t*)c->mine + (size_t)i * planes * chunk;
+        for (size_t pl = 0; pl < planes; pl++, n_rs++)
+          if (c->reduce_scatter(part + pl * pw, mine + pl * chunk, chunk) != 0) throw Fail{SP_E_HIP, "custom reduce_scatter_u32 failed"};
+        hip_ok(hipEventRecord(c->ev_bx[i], c->stream), "hipEventRecord");
+      }
+      for (int i = 0; i < B; i++, n_ag++) {
+        hip_ok(hipStreamWaitEvent(cur[i].main, c->ev_bx[i], 0), "hipStreamWaitEvent");
+        sp_ok(sp_query_fold_local(qs[i], (uint32_t*)c->mine + (size_t)i * planes * chunk, G), "sp_query_fold_local");
+        hip_ok(hipEventRecord(c->ev_f, cur[i].main), "hipEventRecord");
+        hip_ok(hipStreamWaitEvent(c->stream, c->ev_f, 0), "hipStreamWaitEvent");
+        uint64_t* gathered = (uint64_t*)c->gathered + (size_t)i * G * local_words;
+        if (c->all_gather(sp_query_local_cts_ptr(qs[i]), gathered, local_words) != 0) throw Fail{SP_E_HIP, "custom all_gather_u64 failed"};
+        hip_ok(hipEventRecord(c->ev_bg[i], c->stream), "hipEventRecord");
+        hip_ok(hipStreamWaitEvent(cur[i].main, c->ev_bg[i], 0), "hipStreamWaitEvent");
+      }
+      c->rs_recv_bytes = chunk * sizeof(uint32_t);
+      c->ag_send_bytes = local_words * sizeof(uint64_t);
+      c->planes_last = planes;
+      // the next group expands under this group's exchanges and folds
+      if (first + group < n) begin_group(first + group, nxt);
+      for (int i = 0; i < B; i++) {
+        if (c->rank == 0) {
+          size_t len = 0;
+          sp_ok(sp_query_finish_gathered(qs[i], (uint64_t*)c->gathered + (size_t)i * G * local_words, G,
+                                         out + (size_t)(first + i) * out_stride, out_stride, &len),
+                "sp_query_finish_gathered");
+          *out_len = len;
+        } else {
+          sp_ok(sp_query_sync(qs[i]), "sp_query_sync");
+        }
+      }
+      // every reader of this group's regions is done (host waited above); so is the exchange stream before the next group's first collective
+      hip_ok(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+      for (auto& r : cur) sp_query_free(r.q);
+      cur.swap(nxt);
+      nxt.clear();
+    }
+    c->ms[0] = c->ms[1] = c->ms[2] = 0;   // (the per-stage timings belong to the per-query flows)
+    c->last_group = group;
+    c->last_reduce_scatters = n_rs;
+    c->last_all_gathers = n_ag;
+    note_transport(c);
+  });
+  if (rc != SP_OK) (void)hipStreamSynchronize(c->stream);
+  drop(cur);
+  drop(nxt);
   return rc;
 }
 

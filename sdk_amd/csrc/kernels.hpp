@@ -78,7 +78,8 @@ enum PathBit : u64 {
   PATH_FOLD_WAVE8 = 1ull << 30,       // (retired in the round that built it: k_fold_wave8, profiles/r05_fold_wave8.md)
   PATH_SWEEP_PLANAR = 1ull << 31,     // k_sweep_planar: the 9 .. 16-query pass over the digit-planar copy of the database
   PATH_EXPAND_GROUP = 1ull << 32,     // a group's expansions with every round's launches shared (grid dimension = query; r06)
-  PATH_EXPAND_WAVE = 1ull << 33       // k_expand_wave: a round's many-digit side on the wave-per-transform NTT (r06)
+  PATH_EXPAND_WAVE = 1ull << 33,      // k_expand_wave: a round's many-digit side on the wave-per-transform NTT (r06)
+  PATH_SWEEP_BATCH_SCATTER = 1ull << 34 // k_sweep_mfma_scatter: the one-tile batched pass over a row shard, reduce-scatter layout
 };
 // Run-time tunables (sp_debug_set / environment SPIRAL_<NAME>): read on every launch, so that variants can be A/B
 // measured inside one process on ONE database allocation (HBM placement alone moves the sweep by +-5 %).
@@ -439,6 +440,13 @@ inline size_t sweep_batch_rq_words(int nj, int tiles = 1) {
 // form applies and d.rq is set
 void sweep_batch_prepare(const DevTables& T, SweepBatchDesc& d, hipStream_t s);
 void launch_sweep_batch(const DevTables& T, const SweepBatchDesc& d, hipStream_t s);
+// The one-tile matrix-core pass over a ROW SHARD with every query's output in the per-plane reduce-scatter layout
+// [plane][ii % G][r][crt][z][ii / G] (sweep_mfma_scatter.hpp, launched from sweep_planar.hip): d as for launch_sweep_batch after
+// sweep_batch_prepare, out[b] = query b's partial buffer.  _ok: 4 .. 8 queries on a shape the matrix-core form takes, G in {2, 4, 8}.
+constexpr long BATCH_SCATTER_STORE_DEFAULT = 2;
+constexpr long BATCH_SCATTER_MAX_G_DEFAULT = 8;   // largest shard count at which a list left to the library is batched (capi.cpp)
+bool sweep_batch_scatter_ok(const SweepBatchDesc& d, int G);
+void launch_sweep_batch_scatter(const DevTables& T, const SweepBatchDesc& d, int G, hipStream_t s);
 // reference layout -> device layout for a z-range of one plane: src [nz][num_per][dim0] (host-order
 // words already on the device), dst plane base; keeps rows j0..j0+nj
 void launch_db_relayout(u64* dst, int plane, const u64* src, int z0, int nz, int num_per, int dim0, int j0, int nj,

@@ -6,6 +6,7 @@
 #pragma clang diagnostic ignored "-Wunused-function"
 #include "device_common.hpp"
 #include "sweep_planar.hpp"
+#include "sweep_mfma_scatter.hpp"
 #include "server.hpp"
 
 namespace spiral {
@@ -132,6 +133,52 @@ void launch_sweep_planar(const DevTables& T, const SweepBatchDesc& d, hipStream_
   if (eight && ring4) SP_PLANAR(4, 8) else if (eight) SP_PLANAR(2, 8) else if (ring4) SP_PLANAR(4, 4) else SP_PLANAR(2, 4)
 #undef SP_PLANAR
   launched(PATH_SWEEP_BATCH | PATH_SWEEP_MFMA | PATH_SWEEP_MFMA2 | PATH_SWEEP_PLANAR, "k_sweep_planar");
+}
+
+// ---- the one-tile pass over a row shard in the reduce-scatter layout (sweep_mfma_scatter.hpp) --------------------------------
+bool sweep_batch_scatter_ok(const SweepBatchDesc& d, int G) {
+  return tunable("batch_scatter", 1) != 0 && (G == 2 || G == 4 || G == 8) && d.batch <= SWEEP_BATCH_MAX && sweep_batch_wants_mfma(d);
+}
+void launch_sweep_batch_scatter(const DevTables& T, const SweepBatchDesc& d, int G, hipStream_t s) {
+  if (!d.use_mfma || !d.rq || !sweep_batch_scatter_ok(d, G)) throw HipError("internal: the scatter-form batched pass does not take this group");
+  SweepScatterDesc m{};
+  m.db = d.db;
+  m.rq = d.rq;
+  m.rq_off = d.rq + (size_t)N * (d.nj >> 4) * 128 * 4;
+  for (int b = 0; b < d.batch; b++) m.out[b] = d.out[b];
+  for (int b = d.batch; b < SWEEP_BATCH_MAX; b++) m.out[b] = d.out[0];   // never stored to (b < batch in the kernel)
+  m.batch = d.batch;
+  m.planes = d.planes;
+  m.num_per = d.num_per;
+  m.nj = d.nj;
+  m.G = G;
+  m.lgG = G == 2 ? 1 : G == 4 ? 2 : 3;
+  const int chunks = d.num_per >> 7;
+  int cpw = (int)tunable("batch_mfma_cpw", 16);
+  cpw = std::max(1, std::min(cpw, chunks));
+  while (chunks % cpw) cpw--;
+  m.cpw = cpw;
+  const u64 qs[2] = {MODULUS_0, MODULUS_1};
+  for (int c = 0; c < 2; c++) {
+    m.c4[c] = (u32)((1ull << 32) % qs[c]);
+    m.c5[c] = (u32)((1ull << 40) % qs[c]);
+    m.c6[c] = (u32)((1ull << 48) % qs[c]);
+  }
+  const dim3 grid((unsigned)((size_t)d.planes * N * (chunks / cpw)));
+  // store shape: switch batch_scatter_store (1 = dword stores from the registers, 2 = staged through LDS); the default is the
+  // measured winner (profiles/sharded_batch_pass.md)
+  const bool staged = tunable("batch_scatter_store", BATCH_SCATTER_STORE_DEFAULT) == 2;
+  const size_t lds = (size_t)d.nj * 128 + (staged ? SCATTER_STAGE_BYTES : 0);   // one z-row of the digit table (+ the stage)
+#define SP_SCATTER(STORE_)                                                                                              \
+  {                                                                                                                      \
+    if (lds > 65536)                                                                                                     \
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep_mfma_scatter<2, 2, STORE_>),                  \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                              \
+    hipLaunchKernelGGL((k_sweep_mfma_scatter<2, 2, STORE_>), grid, dim3(256), lds, s, T, m);                             \
+  }
+  if (staged) SP_SCATTER(2) else SP_SCATTER(1)
+#undef SP_SCATTER
+  launched(PATH_SWEEP_BATCH | PATH_SWEEP_MFMA | PATH_SCATTER_OUT | PATH_SWEEP_BATCH_SCATTER, "k_sweep_mfma_scatter");
 }
 
 }  // namespace spiral

@@ -313,6 +313,35 @@ class Comm:
             return []
         return [out[k * rb:(k + 1) * rb].tobytes() for k in range(n)]
 
+    def reserve_batch(self, params, group=0):
+        """sp_comm_reserve_batch: reserve() plus the exchange buffers of a batched list in groups of `group` (0 = 8)"""
+        import ctypes as C
+        from .spiral import _chk, lib
+        _chk(lib().sp_comm_reserve_batch(C.c_void_p(self.h), C.c_void_p(params.h), C.c_int(group)))
+
+    def process_queries_batched(self, params, pps, queries, shard, group=0):
+        """sp_process_queries_sharded_batched: the list with ONE pass over the shard per group of up to 8 queries (group = 0:
+        the library's choice, 1 = the per-query flow of process_queries); the list of responses on rank 0, [] elsewhere"""
+        import ctypes as C
+        from .spiral import _bytes, _chk, _p, lib, u8p
+        n = len(queries)
+        if not isinstance(pps, (list, tuple)):
+            pps = [pps] * n
+        bufs = [_bytes(q.data if hasattr(q, "data") else bytes(q)) for q in queries]
+        rb = params.get("response_bytes")
+        out = np.zeros(max(1, n * rb), dtype=np.uint8)
+        ln = C.c_size_t(0)
+        pp_arr = (C.c_void_p * n)(*[pp.h for pp in pps])
+        q_arr = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        l_arr = (C.c_size_t * n)(*[b.size for b in bufs])
+        _chk(lib().sp_process_queries_sharded_batched(C.c_void_p(self.h), C.c_void_p(params.h), pp_arr, q_arr, l_arr, C.c_int(n),
+                                                      C.c_void_p(shard.h), C.c_int(group), _p(out, u8p), C.c_size_t(rb),
+                                                      C.byref(ln)))
+        if ln.value == 0:
+            return []
+        return [out[k * rb:(k + 1) * rb].tobytes() for k in range(n)]
+
+
 
 class NullTransport:
     """Collectives that return at once (no data moves): the custom transport for timing ONE rank's critical path of a
@@ -334,6 +363,7 @@ class LoopbackWorld:
         self.bar = threading.Barrier(world, timeout=300)
         self.slot = [None] * world
         self.done = [None] * world
+        self.calls = [0] * world     # collectives entered per rank (tests: an argument error must enter none)
         self.comms = [Comm.custom(r, world, self._rs(r), self._ag(r)) for r in range(world)]
 
     def comm(self, r):
@@ -343,6 +373,7 @@ class LoopbackWorld:
         """publish (send, ready-event) -> rendezvous -> body(all sends) on my stream after everybody's data is ready ->
         rendezvous -> nobody's stream runs on before every reader of its buffer is done"""
         import torch
+        self.calls[r] += 1
         st = torch.cuda.ExternalStream(stream)
         ev = torch.cuda.Event()
         ev.record(st)

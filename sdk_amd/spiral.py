@@ -525,6 +525,14 @@ class QueryRun:
         _chk(lib().sp_query_sweep_scatter_plane(_vp(self.h), _vp(db.h), C.c_int(G), C.c_int(plane)))
         return self
 
+    @staticmethod
+    def sweep_scatter_group(runs, db, G):
+        """sp_query_sweep_scatter_group: ALL planes of the begun queries `runs` (1 .. 8, begun for row shard `db`) with one pass
+        over the shard; every run's partial buffer then holds what its own sweep_scatter_plane calls would have left"""
+        arr = (C.c_void_p * len(runs))(*[r.h for r in runs])
+        _chk(lib().sp_query_sweep_scatter_group(arr, C.c_int(len(runs)), _vp(db.h), C.c_int(G)))
+        return runs
+
     def fold_local(self, reduced_chunk_ptr, G):
         _chk(lib().sp_query_fold_local(_vp(self.h), C.c_void_p(reduced_chunk_ptr), C.c_int(G)))
         return self
@@ -601,6 +609,16 @@ def bench_sweep_batch(runs, db, iters):
     ms = C.c_float(0)
     arr = (C.c_void_p * len(runs))(*[r.h for r in runs])
     _chk(lib().sp_bench_sweep_batch(arr, C.c_int(len(runs)), _vp(db.h), C.c_int(iters), C.byref(ms)))
+    return ms.value
+
+
+def bench_sweep_scatter_group(runs, db, G, iters, layout=1):
+    """average milliseconds per pass of sweep_scatter_group over row shard `db` (sp_bench_sweep_scatter_group); layout=0 times the
+    plain-layout one-tile pass over the same rows instead (comparison only)"""
+    ms = C.c_float(0)
+    arr = (C.c_void_p * len(runs))(*[r.h for r in runs])
+    _chk(lib().sp_bench_sweep_scatter_group(arr, C.c_int(len(runs)), _vp(db.h), C.c_int(G), C.c_int(layout), C.c_int(iters),
+                                            C.byref(ms)))
     return ms.value
 
 
