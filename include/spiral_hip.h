@@ -372,7 +372,14 @@ int sp_bench_ntt(const sp_params_t*, int M, int blocks, int reps, float* ns_per_
 
 /* ------------------------------------------------------------ stage level
  * 1:1 with the reference's pub functions, operating on caller-owned host arrays in ref layout.
- * These exist for parity tests and for callers (lib/server) that drive stages themselves. */
+ * These exist for parity tests and for callers (lib/server) that drive stages themselves.
+ *
+ * Operand contract.  Operands in NTT form (one residue below its prime per word) must be canonical, < q: the reference's own
+ * pointwise code wraps a u64 on larger words, so there is no defined answer to match.  Raw coefficients, wire words and
+ * database words (lo | hi << 32) may be ANY u64 wherever the reference is exact for them: to_ntt reduces every word mod both
+ * primes; the database loaders and sp_multiply_reg_by_database reduce both 32-bit limbs of `db` and of `v_firstdim` (the
+ * reference sums their products in u128, server.rs:186-217: same residues).  tests/test_gpu_crafted_inputs.py holds the
+ * exports to this. */
 
 /* ntt.rs:67-113 / 212-258: in-place forward / inverse negacyclic NTT of `count` polys (crt*N each) */
 int sp_ntt_forward(const sp_params_t*, uint64_t* data, size_t count);
@@ -399,7 +406,8 @@ int sp_gadget_invert_rdim(const sp_params_t*, const uint64_t* inp, size_t rows_i
 /* util.rs:323-355 reorient_reg_ciphertexts: v_reg[dim0] 2x1 NTT -> out[N*dim0*2] packed lo|hi<<32 */
 int sp_reorient_reg_ciphertexts(const sp_params_t*, const uint64_t* v_reg, uint64_t* out);
 /* server.rs:155-221 multiply_reg_by_database: db = one plane [N][num_per][dim0] (ref layout),
- * v_firstdim = [N][dim0][2]; out = num_per 2x1 NTT cts (ref layout, out[i].data[r*2N + crt*N + z]) */
+ * v_firstdim = [N][dim0][2]; out = num_per 2x1 NTT cts (ref layout, out[i].data[r*2N + crt*N + z]).  Limbs of either
+ * operand may be anything up to 2^32 - 1 (both are reduced on upload). */
 int sp_multiply_reg_by_database(const sp_params_t*, const uint64_t* db, const uint64_t* v_firstdim, size_t dim0,
                                 size_t num_per, uint64_t* out);
 /* server.rs:19-121 coefficient_expansion on v[2^g] 2x1 NTT cts in place (v_w_* from pp; v_neg1 internal) */

@@ -1742,6 +1742,9 @@ int sp_multiply_reg_by_database(const sp_params_t* h, const uint64_t* db, const 
     const int packed = db_can_pack((int)num_per, (int)dim0) && !tunable("db_unpacked", 0) ? 1 : 0;
     launch_db_relayout(d_dev.p, 0, d_ref.p, 0, N, (int)num_per, (int)dim0, 0, (int)dim0, packed, ColMap{}, W->stream);
     upload_raw(*W, v_firstdim, POLY_LEN * dim0 * 2, d_q);
+    // the reference sums limb products in u128 and is exact for any limbs (server.rs:186-217); the sweep kernels sum up to 256
+    // products in u64 and need limbs < q: reduced here, as the loaders reduce the database words (same residues)
+    launch_canon_words(d_q.p, POLY_LEN * dim0 * 2, W->stream);
     SweepDesc d{d_dev.p, d_q.p, d_res.p, 1, (int)num_per, (int)dim0, 0, (int)dim0, packed, 1};
     launch_sweep(W->D->T, d, W->stream);
     launch_sweep_out_to_ref(d_out.p, d_res.p, (int)num_per, W->stream);

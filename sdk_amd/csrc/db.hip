@@ -243,6 +243,18 @@ void launch_db_encode(const DevTables& T, const DbEncodeDesc& d, hipStream_t s) 
   launched(0, "k_db_encode");
 }
 
+// caller-owned query words of the stage export (sp_multiply_reg_by_database): both limbs reduced in place, as
+// k_interleave_query reduces the wire words of a direct-upload query
+__global__ __launch_bounds__(256) void k_canon_words(u64* w, size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < total) w[i] = canon_word(w[i]);
+}
+void launch_canon_words(u64* w, size_t total, hipStream_t s) {
+  if (total == 0) return;
+  hipLaunchKernelGGL(k_canon_words, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, total);
+  launched(0, "k_canon_words");
+}
+
 __global__ __launch_bounds__(256) void k_sweep_out_to_ref(u64* out, const u32* in, int num_per) {
   // out[ii][r][crt][z] <- in[r][crt][z][ii]
   size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

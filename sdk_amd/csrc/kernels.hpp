@@ -451,6 +451,8 @@ void launch_sweep_batch_scatter(const DevTables& T, const SweepBatchDesc& d, int
 // words already on the device), dst plane base; keeps rows j0..j0+nj
 void launch_db_relayout(u64* dst, int plane, const u64* src, int z0, int nz, int num_per, int dim0, int j0, int nj,
                         int packed, ColMap cm, hipStream_t s);
+// both 32-bit limbs of `total` lo | hi << 32 words reduced mod q0 / q1 in place (canon_word)
+void launch_canon_words(u64* w, size_t total, hipStream_t s);
 void launch_db_synth(u64* dst, u64 seed, int planes, int num_per, int dim0, int j0, int nj, int packed, ColMap cm,
                      hipStream_t s);
 // read back words (plane, z, ii, j_local0 .. +count) of either device format into out[count] (device)

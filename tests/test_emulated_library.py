@@ -3,7 +3,7 @@
 tests/emu/ builds sdk_amd/csrc unchanged for the host (a stand-in <hip/hip_runtime.h>: workgroups as fibers, barriers and
 wave exchanges as scheduling points, device memory = host memory, gfx950 builtins restated in C) into
 tests/emu/_build/libspiral_emu.so with the C ABI of libspiral_hip.so.  The tests below run a subset of the `-m gpu` parity
-tests (tests/test_gpu_parity.py and tests/test_sparse_bucket.py, byte comparisons with the oracle) against that build in a
+tests (tests/test_gpu_parity.py, tests/test_sparse_bucket.py and tests/test_gpu_crafted_inputs.py, byte comparisons with the oracle) against that build in a
 child process (SPIRAL_HIP_LIB selects the library file), once more under AddressSanitizer, where every device buffer is a heap block with
 red zones: an out-of-bounds read or write of any kernel on these shapes is an error, which no GPU run can show.
 
@@ -52,6 +52,25 @@ SPARSE_SUBSET = ("(test_sparse_deep_columns and nu1_8) or (test_sparse_empty_col
 SPARSE_LONG_SUBSET = ("test_sparse_empty_column_patterns or test_sparse_zero_and_short_items or test_sparse_pruned_expansion_row_sets "
                       "or test_sparse_index_rebuilds_and_snapshots or test_sparse_bucket_query_lists")
 ASAN_SPARSE_SUBSET = "test_sparse_empty_column_patterns and left_half_empty and inst2"
+# crafted client inputs (tests/test_gpu_crafted_inputs.py), small shapes: wire words at the reduction's boundaries through
+# sp_pp_deserialize and a single query (28-bit gadget digits included), limbs above q in a direct-upload query, in both operands of
+# sp_multiply_reg_by_database (512 x 32 and 300 x 128: more rows than one block of the sweeps' u64 sums) and in
+# sp_db_load, the fold exports at their accumulators' corners, sp_encode's rounding boundaries
+CRAFTED_SUBSET = ("(test_pp_deserialize_crafted and fast and not fast56 and (ones or kQ-1 or full)) "
+                  "or (test_single_query_crafted and fast and not fast56 and (ones or const_max)) "
+                  "or (test_single_query_crafted and fuzz11 and digits_max) "
+                  "or (test_direct_upload_crafted and fast-direct and (limbs-2 or full)) "
+                  "or (test_multiply_reg_by_database_any_limbs and (512-32 or 300-128) and db_canonical) "
+                  "or (test_multiply_reg_by_database_any_limbs and 1024-128 and db_top) "
+                  "or test_db_load_any_limbs or (test_fold_exports_at_accumulator_corners and 2-0) "
+                  "or (test_encode_rounding_boundaries and 20-256) or test_multiply_export_all_top")
+CRAFTED_LONG_SUBSET = ("test_pp_deserialize_crafted or (test_single_query_crafted and (fast or fuzz11)) or (test_direct_upload_crafted and not wide) "
+                       "or (test_multiply_reg_by_database_any_limbs and not 1024 and not 2048) or test_fold_exports_at_accumulator_corners "
+                       "or test_encode_rounding_boundaries or test_expansion_conversion_pack_exports or test_sparse_bucket_crafted "
+                       "or (test_query_lists_crafted_members and narrow) or (test_matrix_core_pass_both_operands_extreme and one-tile-64)")
+ASAN_CRAFTED_SUBSET = ("(test_multiply_reg_by_database_any_limbs and 300-128 and db_canonical-q_ones) or (test_db_load_any_limbs and packed) "
+                       "or (test_direct_upload_crafted and fast-direct and limbs-high) or (test_pp_deserialize_crafted and fast56 and ones) "
+                       "or (test_single_query_crafted and fast and not fast56 and full)")
 
 
 def _run(lib, expr, extra_env=None, timeout=1500, at_least=5, test_file="test_gpu_parity.py"):
@@ -86,6 +105,19 @@ def test_sparse_bucket_subset_on_the_emulated_device(emulated):
     """lib/server's sparse caller (sp_db_create_sparse + sp_db_update_item: k_sparse_item_encode, k_sweep_sparse, the pruned
     expansion, the fused fold with its all-zero shortcuts) against the oracle, with the streams in `starve:1` order"""
     assert _run(emulated, SPARSE_SUBSET, {"SPIRAL_EMU_STREAMS": "starve:1"}, at_least=3, test_file="test_sparse_bucket.py") >= 3
+
+
+def test_crafted_inputs_subset_on_the_emulated_device(emulated):
+    """words no honest client sends (tests/test_gpu_crafted_inputs.py) through the kernels' source, against the oracle on the
+    same crafted bytes"""
+    assert _run(emulated, CRAFTED_SUBSET, at_least=18, test_file="test_gpu_crafted_inputs.py") >= 18
+
+
+@long_only
+def test_crafted_inputs_cases_on_the_emulated_device(emulated):
+    """every family on the small configurations, a list with crafted members, a sparse bucket, the matrix-core pass with both
+    operands at their digit extremes (64 rows)"""
+    assert _run(emulated, CRAFTED_LONG_SUBSET, at_least=240, timeout=6000, test_file="test_gpu_crafted_inputs.py") >= 240
 
 
 @long_only
@@ -133,6 +165,7 @@ def test_kernels_stay_inside_their_buffers(emulated):
     try:
         _run(so, ASAN_SUBSET, env)
         _run(so, ASAN_SPARSE_SUBSET, env, at_least=1, test_file="test_sparse_bucket.py")
+        _run(so, ASAN_CRAFTED_SUBSET, env, at_least=5, test_file="test_gpu_crafted_inputs.py")
     finally:
         reports = [f for f in os.listdir(emu_build.BUILD) if f.startswith("asan_report")]
         if reports:
