@@ -1,152 +1,39 @@
-// extern "C" surface of libspiral_hip.so (include/spiral_hip.h).
-#include <chrono>
+// extern "C" surface of libspiral_hip.so (include/spiral_hip.h): the error boundary, params, databases, public parameters, the query
+// stage machine and sp_process_query.  The list flows are in capi_batch.cpp, the stage-level exports in capi_stage.cpp.
 #include <cstdlib>
-#include <cstring>
-#include <deque>
 #include <new>
 
-#include "../../include/spiral_hip.h"
-#include "pipeline.hpp"
+#include "capi_internal.hpp"
 
 using namespace spiral;
 
 static thread_local std::string g_last_error;
 static thread_local int g_last_rc = SP_OK;  // status of this thread's last guarded() section: what a constructor-style entry
                                              // point (returns a handle or null) failed with
-
-template <typename F>
-static int guarded(F&& f) {
-  tunables_new_call();
-  auto fail = [](int rc, const char* what) {
-    g_last_error = what;
-    g_last_rc = rc;
-    return rc;
-  };
-  try {
-    f();
-    g_last_rc = SP_OK;
-    return SP_OK;
-  } catch (const ArgError& e) {
-    return fail(SP_E_ARG, e.what());
-  } catch (const OomError& e) {
-    return fail(SP_E_OOM, e.what());
-  } catch (const HipError& e) {
-    return fail(SP_E_HIP, e.what());
-  } catch (const std::bad_alloc&) {
-    return fail(SP_E_OOM, "host allocation failed");
-  } catch (const std::exception& e) {
-    return fail(SP_E_ARG, e.what());
-  }
+int spiral::guarded_status(int rc, const char* what) {
+  if (rc != SP_OK) g_last_error = what;
+  g_last_rc = rc;
+  return rc;
 }
-// a pair of timing events that cannot leak
-struct TimingEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  TimingEvents() {
-    HIP_CHECK(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) {
-      (void)hipEventDestroy(a);
-      throw HipError("hipEventCreate failed");
-    }
-  }
-  ~TimingEvents() {
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-  }
-  TimingEvents(const TimingEvents&) = delete;
-  TimingEvents& operator=(const TimingEvents&) = delete;
-};
-// status to report when a handle-returning entry point came back null
-static int null_handle_rc() { return g_last_rc != SP_OK ? g_last_rc : SP_E_ARG; }
+int spiral::null_handle_rc() { return g_last_rc != SP_OK ? g_last_rc : SP_E_ARG; }
 
-struct sp_query {
-  sp_params* params = nullptr;
-  const sp_pp* pp = nullptr;
-  std::unique_ptr<Workspace> ws;
-  int state = 0;  // 1 begun, 2 swept, 3 finished
-  int next_plane = 0;  // sp_query_sweep_scatter_plane progress
-  int next_fold_plane = 0;  // sp_query_fold_local_plane progress
-  int rows_j0 = 0, rows_nj = 0;  // sp_query_begin_for_db on a row shard: only these first-dimension rows were expanded
-  const sp_db* for_sparse = nullptr;  // begun for this sparse bucket: only the rows holding items were expanded
-  std::shared_ptr<const sp_db::SparseIndex> sparse_index;  // ... with this snapshot of its index (kept until the query is freed)
-  std::shared_ptr<const DevBuf<u64>> planar;  // the digit-planar copy a batched group's pass on this (first) workspace reads: pinned
-                                              // until the query is freed, i.e. until after its stream has been synchronised
-  float ms[4] = {0, 0, 0, 0};
-  bool streams_idle = false;  // the owner has waited for the main stream after the last enqueue (which orders stream2's work before it)
-  ~sp_query() {
-    if (ws && params) {
-      if (!streams_idle) {
-        (void)hipStreamSynchronize(ws->stream);
-        (void)hipStreamSynchronize(ws->stream2);
-      }
-      ws->pipelined = false;
-      ws->have_sweep_span = false;
-      ws->zero_shortcuts = false;
-      params->release_ws(std::move(ws));
-    }
-  }
-};
-
-namespace {
-
-struct Scoped {  // a workspace borrowed for one stage-level call
-  sp_params* P;
-  std::unique_ptr<Workspace> ws;
-  explicit Scoped(const sp_params* p) : P(const_cast<sp_params*>(p)), ws(P->acquire_ws()) {}
-  ~Scoped() {
-    (void)hipStreamSynchronize(ws->stream);
-    P->release_ws(std::move(ws));
-  }
-  Workspace& operator*() { return *ws; }
-  Workspace* operator->() { return ws.get(); }
-};
-
-void need(bool c, const char* msg) {
-  if (!c) throw ArgError(msg);
-}
-
-// host u64 NTT words -> device u32
-void upload_ntt(Workspace& W, const uint64_t* host, size_t words, DevBuf<u32>& dst, DevBuf<u64>& tmp) {
-  tmp.ensure(words);
-  dst.ensure(words);
-  HIP_CHECK(hipMemcpyAsync(tmp.p, host, words * 8, hipMemcpyHostToDevice, W.stream));
-  launch_u64_to_u32(dst.p, tmp.p, (long)words, W.stream);
-}
-void download_ntt(Workspace& W, const u32* src, size_t words, uint64_t* host, DevBuf<u64>& tmp) {
-  tmp.ensure(words);
-  launch_u32_to_u64(tmp.p, src, (long)words, W.stream);
-  HIP_CHECK(hipMemcpyAsync(host, tmp.p, words * 8, hipMemcpyDeviceToHost, W.stream));
-  HIP_CHECK(hipStreamSynchronize(W.stream));
-}
-void upload_raw(Workspace& W, const uint64_t* host, size_t words, DevBuf<u64>& dst) {
-  dst.ensure(words);
-  HIP_CHECK(hipMemcpyAsync(dst.p, host, words * 8, hipMemcpyHostToDevice, W.stream));
-}
-void download_raw(Workspace& W, const u64* src, size_t words, uint64_t* host) {
-  HIP_CHECK(hipMemcpyAsync(host, src, words * 8, hipMemcpyDeviceToHost, W.stream));
-  HIP_CHECK(hipStreamSynchronize(W.stream));
-}
-
-// the fold buffers of a stage-level fold export grown to `num_per` ciphertexts and `further` levels (the workspace was sized for
-// the params' own num_per)
-void ensure_stage_fold(Workspace& W, size_t num_per, size_t further) {
-  const size_t two_t = 2 * W.P->t_gsw;
-  W.ensure_expand();
-  W.foldX.ensure(num_per * 2 * POLY_LEN);
-  W.foldY.ensure(std::max<size_t>(num_per / 2, 1) * 2 * POLY_LEN);
-  W.fold_dig.ensure(num_per * two_t * 2 * POLY_LEN);
-  W.fold_ntt.ensure(std::max<size_t>(num_per / 2, 1) * 2 * 2 * POLY_LEN);
-  W.fold_mats.ensure(further * 2 * 2 * two_t * 2 * POLY_LEN);
-}
-
-void check_device(int dev) {
+void spiral::check_device(int dev) {
   int cur = 0;
   HIP_CHECK(hipGetDevice(&cur));
   if (cur != dev) throw ArgError("handle belongs to HIP device " + std::to_string(dev) + " but the current device is " + std::to_string(cur));
 }
 
-// what one workspace of a batched group may need, as the group planner and the planar copy estimate it: three times the
-// first-dimension output (a rough bound; pooled workspaces only make it conservative)
-size_t group_ws_bytes(const Params& p, int np_local) { return (size_t)3 * p.planes() * 4 * POLY_LEN * (size_t)np_local * sizeof(u32); }
+void spiral::download_ntt(Workspace& W, const u32* src, size_t words, uint64_t* host, DevBuf<u64>& tmp) {
+  tmp.ensure(words);
+  launch_u32_to_u64(tmp.p, src, (long)words, W.stream);
+  HIP_CHECK(hipMemcpyAsync(host, tmp.p, words * 8, hipMemcpyDeviceToHost, W.stream));
+  HIP_CHECK(hipStreamSynchronize(W.stream));
+}
+
+// three times the first-dimension output (a rough bound; pooled workspaces only make it conservative)
+size_t spiral::group_ws_bytes(const Params& p, int np_local) { return (size_t)3 * p.planes() * 4 * POLY_LEN * (size_t)np_local * sizeof(u32); }
+
+namespace {
 
 // bits per plaintext coefficient (ceil log2 p) and bytes of an item per plane (params.rs:188-193) of the database encoder
 size_t pt_bits(const Params& p) {
@@ -185,13 +72,9 @@ const uint8_t* upload_item(sp_db& d, const uint8_t* data, size_t len) {
   return d.upload.p;
 }
 
-using PlanarPin = std::shared_ptr<const DevBuf<u64>>;
+}  // namespace
 
-// One batched pass of the group qs[0 .. B) over `db`, run on the first query's stream: the database, the queries' operands and
-// outputs; on the matrix cores the group's query digit table with the first workspace (allocated on its first batched call, then
-// reused) and, for two query tiles, the digit-planar copy -- pinned in `pin`, which the caller holds until that stream has been
-// synchronised.
-SweepBatchDesc group_pass(const sp_db& db, sp_query_t* const* qs, int B, bool use_planar, PlanarPin& pin) {
+SweepBatchDesc spiral::group_pass(const sp_db& db, sp_query_t* const* qs, int B, bool use_planar, PlanarPin& pin) {
   const Params& p = db.params->p;
   Workspace& W0 = *qs[0]->ws;
   SweepBatchDesc d{};
@@ -214,8 +97,16 @@ SweepBatchDesc group_pass(const sp_db& db, sp_query_t* const* qs, int B, bool us
   d.planar = pin ? reinterpret_cast<const unsigned char*>(pin->p) : nullptr;
   return d;
 }
-
-}  // namespace
+Workspace& spiral::group_pass_stream(sp_query_t* const* qs, int B) {
+  Workspace& W0 = *qs[0]->ws;
+  for (int i = 1; i < B; i++) HIP_CHECK(hipStreamWaitEvent(W0.stream, qs[i]->ws->ev[1], 0));
+  return W0;
+}
+void spiral::group_pass_done(sp_query_t* const* qs, int i) {
+  Workspace& W = *qs[i]->ws;
+  if (i > 0) HIP_CHECK(hipStreamWaitEvent(W.stream, qs[0]->ws->ev[2], 0));
+  HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
+}
 
 // The digit-planar copy of a PACKED, unsharded database (sweep_planar.hpp): what the 9 .. 16-query pass reads.  Built by
 // sp_db_prepare_batch (at load time) or on first use (one gather pass over the PACKED units), only when the device has the room for
@@ -293,6 +184,103 @@ std::shared_ptr<const sp_db::SparseIndex> sp_db::ensure_sparse_index() {
   return sparse_index;
 }
 
+// ---- pieces of the query stage machine (below) that are not entry points themselves
+// the head of every query: the handles checked, a sparse bucket's index snapshot taken, the workspace acquired and the "begin" event
+// recorded; state 0
+static std::unique_ptr<sp_query> open_query(const sp_params_t* h, const sp_pp_t* pp, const sp_db_t* db) {
+  need(h && pp, "null argument");
+  need(pp->params == h, "public parameters were created for different params");
+  need(!db || db->params == h, "db was created for different params");
+  check_device(pp->device);
+  auto q = std::make_unique<sp_query>();
+  if (db && db->sparse) q->sparse_index = const_cast<sp_db*>(db)->ensure_sparse_index();
+  q->params = const_cast<sp_params*>(h);
+  q->pp = pp;
+  q->ws = q->params->acquire_ws();
+  HIP_CHECK(hipEventRecord(q->ws->ev[0], q->ws->stream));
+  return q;
+}
+sp_query_t* spiral::query_open(const sp_params_t* h, const sp_pp_t* pp) {
+  return guarded_handle([&] { return open_query(h, pp, nullptr); });
+}
+
+// a begun query goes over `db` only if it was expanded for every row, or for the rows of exactly this row shard
+static void need_rows_of(const sp_query_t* q, const sp_db_t* db) {
+  need(q->rows_nj == 0 || (db->col_G == 1 && db->j0 == q->rows_j0 && db->nj == q->rows_nj),
+       "the query was expanded for another row shard (sp_query_begin_for_db)");
+}
+// the shard count of the scatter sweeps (with `db`: it is one of G shards) and of the local folds
+static void need_shard_count(const Params& p, int G, const sp_db_t* db = nullptr) {
+  const bool ok = G >= 1 && (G & (G - 1)) == 0 && (size_t)G <= p.num_per() && G <= SP_MAX_ROW_SHARDS;
+  if (!db) return need(ok, "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS)");
+  need(ok && db->num_shards == G, "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS) and equal to the db's num_shards");
+}
+static void need_row_shard(const sp_db_t* db) { need(db->col_G == 1 && !db->sparse, "sweep_scatter works on row shards"); }
+// the workspace's first-dimension output in the reduce-scatter layout of G shards while the scope's sweep launches are enqueued:
+// plain again on every path out of it, so that the workspace never goes on to another stage, or back to the pool, in scatter layout
+struct ScatterLayout {
+  Workspace& W;
+  ScatterLayout(Workspace& w, int G) : W(w) { W.out_G = G; }
+  ~ScatterLayout() { W.out_G = 1; }
+};
+
+void spiral::scatter_group_check(sp_query_t* const* qs, int batch, const sp_db_t* db, int G) {
+  need(qs && db, "null argument");
+  need(batch >= 1 && batch <= SWEEP_BATCH_MAX, "sp_query_sweep_scatter_group: 1 .. 8 queries per pass");
+  need_row_shard(db);
+  need_shard_count(db->params->p, G, db);
+  for (int i = 0; i < batch; i++) {
+    need(qs[i] && qs[i]->ws, "null query");
+    need(qs[i]->params == db->params, "db was created for different params");
+    need_rows_of(qs[i], db);
+    for (int k = 0; k < i; k++) need(qs[k] != qs[i], "sp_query_sweep_scatter_group: the same query twice");
+  }
+  check_device(db->device);
+}
+bool spiral::scatter_group_desc(sp_query_t* const* qs, int batch, const sp_db_t* db, int G, SweepBatchDesc& d) {
+  for (int i = 0; i < batch; i++) qs[i]->ws->ensure_sweep();
+  if (!db->packed || G < 2) return false;
+  PlanarPin none;
+  d = group_pass(*db, qs, batch, false, none);
+  return d.rq != nullptr && sweep_batch_scatter_ok(d, G);
+}
+
+// the end of both finishing calls: wait for the stream, the response out, the stage timings (the spans between the workspace's
+// five events) in
+static void collect_response(sp_query_t* q, uint8_t* out, size_t* out_len) {
+  const Workspace& W = *q->ws;
+  HIP_CHECK(hipStreamSynchronize(W.stream));
+  *out_len = q->params->p.response_bytes();
+  memcpy(out, W.h_response, *out_len);
+  for (int k = 0; k < 4; k++) {
+    float t = 0;
+    HIP_CHECK(hipEventElapsedTime(&t, W.ev[k], W.ev[k + 1]));
+    q->ms[k] = t;
+  }
+}
+
+void spiral::finish_impl(sp_query_t* q, bool premod, uint8_t* out, size_t out_cap, size_t* out_len) {
+  need(q && out && out_len, "null argument");
+  need(q->state == 2, "sp_query_finish: sweep has not run");
+  const Params& p = q->params->p;
+  need(out_cap >= p.response_bytes(), "output buffer smaller than response_bytes");
+  Workspace& W = *q->ws;
+  debug_stage(3);
+  run_finish(W, *q->pp, premod);
+  collect_response(q, out, out_len);
+  if (W.have_sweep_span) {
+    // pipelined sweeps: [1] = first sweep launch begins -> last sweep launch done (on the stream that carries them),
+    // [2] = what is left of the span expanded -> folded (the exposed part of the last plane's fold)
+    float sw = 0, tot = 0;
+    HIP_CHECK(hipEventElapsedTime(&sw, W.ev_sw[0], W.ev_sw[1]));
+    HIP_CHECK(hipEventElapsedTime(&tot, W.ev[1], W.ev[3]));
+    q->ms[1] = sw;
+    q->ms[2] = tot > sw ? tot - sw : 0.f;
+    W.have_sweep_span = false;
+  }
+  q->state = 3;
+}
+
 extern "C" {
 
 const char* sp_last_error(void) { return g_last_error.c_str(); }
@@ -347,14 +335,12 @@ int sp_set_device(int device) {
 
 // ------------------------------------------------------------------------------------ Params
 sp_params_t* sp_params_from_json(const char* json) {
-  sp_params_t* out = nullptr;
-  int rc = guarded([&] {
+  return guarded_handle([&] {
     need(json != nullptr, "json is null");
     auto h = std::make_unique<sp_params>();
     h->p = Params::from_json(json);
-    out = h.release();
+    return h;
   });
-  return rc == SP_OK ? out : nullptr;
 }
 void sp_params_free(sp_params_t* p) { delete p; }
 
@@ -402,8 +388,7 @@ int sp_params_ntt_table(const sp_params_t* h, int crt, int which, uint64_t* out_
 
 // ---------------------------------------------------------------------------------------- DB
 static sp_db_t* db_create_impl(const sp_params_t* h, int shard, int num_shards, bool by_columns) {
-  sp_db_t* out = nullptr;
-  int rc = guarded([&] {
+  return guarded_handle([&] {
     need(h != nullptr, "params is null");
     const Params& p = h->p;
     need(num_shards >= 1 && shard >= 0 && shard < num_shards, "bad shard");
@@ -439,14 +424,12 @@ static sp_db_t* db_create_impl(const sp_params_t* h, int shard, int num_shards, 
     // and removed: profiles/r03_placement.md.)
     HIP_CHECK(hipMemset(d->words.p, 0, d->words.bytes()));  // an empty bucket: absent items are zero polynomials
     const_cast<sp_params*>(h)->device_state();
-    out = d.release();
+    return d;
   });
-  return rc == SP_OK ? out : nullptr;
 }
 // lib/server's SparseDb (lib/server/src/db/sparse_db.rs:5-48): an empty bucket that stores only the items written to it
 sp_db_t* sp_db_create_sparse(const sp_params_t* h) {
-  sp_db_t* out = nullptr;
-  int rc = guarded([&] {
+  return guarded_handle([&] {
     need(h != nullptr, "params is null");
     const Params& p = h->p;
     need(p.expand_queries, "sparse buckets serve expanded queries (lib/server's sparse path, server.rs:31-33)");
@@ -458,9 +441,8 @@ sp_db_t* sp_db_create_sparse(const sp_params_t* h) {
     d->nj = (int)p.dim0();
     d->np_local = (int)p.num_per();
     const_cast<sp_params*>(h)->device_state();
-    out = d.release();
+    return d;
   });
-  return rc == SP_OK ? out : nullptr;
 }
 size_t sp_db_sparse_items(const sp_db_t* d) {
   if (!d || !d->sparse) return 0;
@@ -672,8 +654,7 @@ int sp_db_read_ref(const sp_db_t* d, int plane, int z, int ii, int j0, int count
 
 // ------------------------------------------------------------------------- PublicParameters
 sp_pp_t* sp_pp_deserialize(const sp_params_t* h, const uint8_t* data, size_t len) {
-  sp_pp_t* out = nullptr;
-  int rc = guarded([&] {
+  return guarded_handle([&] {
     need(h && data, "null argument");
     const Params& p = h->p;
     if (len != p.setup_bytes()) throw ArgError("public parameter length " + std::to_string(len) + " != setup_bytes " + std::to_string(p.setup_bytes()));
@@ -742,9 +723,8 @@ sp_pp_t* sp_pp_deserialize(const sp_params_t* h, const uint8_t* data, size_t len
       h2d_sync(pp->all_w.p + off * 2 * POLY_LEN, zero_one.data(), zero_one.size() * sizeof(u32));
     }
     HIP_CHECK(hipDeviceSynchronize());
-    out = pp.release();
+    return pp;
   });
-  return rc == SP_OK ? out : nullptr;
 }
 void sp_pp_free(sp_pp_t* p) { delete p; }
 
@@ -762,50 +742,18 @@ int sp_pp_export(const sp_pp_t* pp, uint64_t* out, size_t cap_words, size_t* n_w
 }
 
 // ------------------------------------------------------------------------------ process_query
-// a query object with its workspace, nothing enqueued yet but the "begin" event (the group flow of sp_process_query_batch, which
-// expands its queries together: run_begin_group); state 0 until the caller has begun it
-static sp_query_t* query_open(const sp_params_t* h, const sp_pp_t* pp) {
-  sp_query_t* out = nullptr;
-  int rc = guarded([&] {
-    need(h && pp, "null argument");
-    need(pp->params == h, "public parameters were created for different params");
-    check_device(pp->device);
-    auto q = std::make_unique<sp_query>();
-    q->params = const_cast<sp_params*>(h);
-    q->pp = pp;
-    q->ws = q->params->acquire_ws();
-    HIP_CHECK(hipEventRecord(q->ws->ev[0], q->ws->stream));
-    out = q.release();
-  });
-  return rc == SP_OK ? out : nullptr;
-}
-
 sp_query_t* sp_query_begin(const sp_params_t* h, const sp_pp_t* pp, const uint8_t* query, size_t query_len) {
   return sp_query_begin_for_db(h, pp, query, query_len, nullptr);
 }
 
 sp_query_t* sp_query_begin_for_db(const sp_params_t* h, const sp_pp_t* pp, const uint8_t* query, size_t query_len,
                                   const sp_db_t* db) {
-  sp_query_t* out = nullptr;
-  int rc = guarded([&] {
+  return guarded_handle([&] {
     need(h && pp && query, "null argument");
-    need(pp->params == h, "public parameters were created for different params");
-    need(!db || db->params == h, "db was created for different params");
-    check_device(pp->device);
-    const bool rows = db && db->num_shards > 1 && db->col_G == 1;
-    const DeviceState::PrunedPlan* plan = nullptr;
-    std::shared_ptr<const sp_db::SparseIndex> snap;
-    if (db && db->sparse) {
-      snap = const_cast<sp_db*>(db)->ensure_sparse_index();
-      plan = snap->plan.get();
-    }
-    auto q = std::make_unique<sp_query>();
-    q->sparse_index = snap;
-    q->params = const_cast<sp_params*>(h);
-    q->pp = pp;
-    q->ws = q->params->acquire_ws();
+    auto q = open_query(h, pp, db);
     Workspace& W = *q->ws;
-    HIP_CHECK(hipEventRecord(W.ev[0], W.stream));
+    const bool rows = db && db->num_shards > 1 && db->col_G == 1;
+    const DeviceState::PrunedPlan* plan = q->sparse_index ? q->sparse_index->plan.get() : nullptr;
     // a long (per-plane, pipelined) sweep follows: worth moving the fold's half of the expansion off the critical path
     // (r06: also before the per-plane sweeps of a ROW SHARD -- the multi-GPU flows: the even subtree, pruned to the shard's rows,
     // is short there, and the odd subtree + GSW side, which only the fold needs, then runs beside the sweeps and their exchanges
@@ -826,9 +774,8 @@ sp_query_t* sp_query_begin_for_db(const sp_params_t* h, const sp_pp_t* pp, const
     q->for_sparse = db && db->sparse ? db : nullptr;
     q->rows_j0 = rows ? db->j0 : 0;
     q->rows_nj = rows ? db->nj : 0;
-    out = q.release();
+    return q;
   });
-  return rc == SP_OK ? out : nullptr;
 }
 
 int sp_query_sweep(sp_query_t* q, const sp_db_t* db) {
@@ -836,8 +783,7 @@ int sp_query_sweep(sp_query_t* q, const sp_db_t* db) {
     need(q && db, "null argument");
     need(q->state == 1, "sp_query_sweep: query not in 'begun' state");
     need(db->params == q->params, "db was created for different params");
-    need(q->rows_nj == 0 || (db->col_G == 1 && db->j0 == q->rows_j0 && db->nj == q->rows_nj),
-         "the query was expanded for another row shard (sp_query_begin_for_db)");
+    need_rows_of(q, db);
     check_device(db->device);
     Workspace& W = *q->ws;
     need(q->for_sparse == nullptr || q->for_sparse == db, "the query was expanded for another sparse bucket");
@@ -863,17 +809,13 @@ int sp_query_sweep_scatter(sp_query_t* q, const sp_db_t* db, int G) {
     need(q && db, "null argument");
     need(q->state == 1, "sp_query_sweep_scatter: query not in 'begun' state");
     need(db->params == q->params, "db was created for different params");
-    need(q->rows_nj == 0 || (db->col_G == 1 && db->j0 == q->rows_j0 && db->nj == q->rows_nj),
-         "the query was expanded for another row shard (sp_query_begin_for_db)");
-    const Params& p = q->params->p;
-    need(G >= 1 && (G & (G - 1)) == 0 && (size_t)G <= p.num_per() && db->num_shards == G && G <= SP_MAX_ROW_SHARDS,
-         "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS) and equal to the db's num_shards");
-    need(db->col_G == 1 && !db->sparse, "sweep_scatter works on row shards");
+    need_rows_of(q, db);
+    need_shard_count(q->params->p, G, db);
+    need_row_shard(db);
     check_device(db->device);
     Workspace& W = *q->ws;
-    W.out_G = G;
+    ScatterLayout scatter(W, G);
     run_sweep(W, *db);
-    W.out_G = 1;
     HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
     q->state = 2;
   });
@@ -883,25 +825,17 @@ int sp_query_sweep_scatter_plane(sp_query_t* q, const sp_db_t* db, int G, int pl
   return guarded([&] {
     need(q && db, "null argument");
     need(db->params == q->params, "db was created for different params");
-    need(q->rows_nj == 0 || (db->col_G == 1 && db->j0 == q->rows_j0 && db->nj == q->rows_nj),
-         "the query was expanded for another row shard (sp_query_begin_for_db)");
+    need_rows_of(q, db);
     const Params& p = q->params->p;
-    need(G >= 1 && (G & (G - 1)) == 0 && (size_t)G <= p.num_per() && db->num_shards == G && G <= SP_MAX_ROW_SHARDS,
-         "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS) and equal to the db's num_shards");
-    need(db->col_G == 1 && !db->sparse, "sweep_scatter works on row shards");
+    need_shard_count(p, G, db);
+    need_row_shard(db);
     need(plane >= 0 && (size_t)plane < p.planes(), "plane out of range");
     need(q->state == 1 && q->next_plane == plane, "sp_query_sweep_scatter_plane: planes must be swept in order after begin");
     check_device(db->device);
     Workspace& W = *q->ws;
     W.ensure_sweep();
-    W.out_G = G;
-    try {
-      launch_plane_sweep(W, *db, (size_t)plane);
-    } catch (...) {
-      W.out_G = 1;
-      throw;
-    }
-    W.out_G = 1;
+    ScatterLayout scatter(W, G);
+    launch_plane_sweep(W, *db, (size_t)plane);
     q->next_plane = plane + 1;
     if ((size_t)q->next_plane == p.planes()) {
       HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
@@ -912,32 +846,6 @@ int sp_query_sweep_scatter_plane(sp_query_t* q, const sp_db_t* db, int G, int pl
 
 // One pass over the row shard for a whole group (the stage between sp_query_begin_for_db and sp_query_fold_local of the batched
 // sharded list, comm.cpp).  Checks first, nothing enqueued on an error.
-static void scatter_group_check(sp_query_t* const* qs, int batch, const sp_db_t* db, int G) {
-  need(qs && db, "null argument");
-  need(batch >= 1 && batch <= SWEEP_BATCH_MAX, "sp_query_sweep_scatter_group: 1 .. 8 queries per pass");
-  const Params& p = db->params->p;
-  need(db->col_G == 1 && !db->sparse, "sweep_scatter works on row shards");
-  need(G >= 1 && (G & (G - 1)) == 0 && (size_t)G <= p.num_per() && db->num_shards == G && G <= SP_MAX_ROW_SHARDS,
-       "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS) and equal to the db's num_shards");
-  for (int i = 0; i < batch; i++) {
-    need(qs[i] && qs[i]->ws, "null query");
-    need(qs[i]->params == db->params, "db was created for different params");
-    need(qs[i]->rows_nj == 0 || (db->j0 == qs[i]->rows_j0 && db->nj == qs[i]->rows_nj),
-         "the query was expanded for another row shard (sp_query_begin_for_db)");
-    for (int k = 0; k < i; k++) need(qs[k] != qs[i], "sp_query_sweep_scatter_group: the same query twice");
-  }
-  check_device(db->device);
-}
-// the group's pass in the reduce-scatter layout on the first query's stream (prepared descriptor); false: this group or shape is
-// not the matrix-core pass's -- the caller sweeps per query
-static bool scatter_group_desc(sp_query_t* const* qs, int batch, const sp_db_t* db, int G, SweepBatchDesc& d) {
-  for (int i = 0; i < batch; i++) qs[i]->ws->ensure_sweep();
-  if (!db->packed || G < 2) return false;
-  PlanarPin none;
-  d = group_pass(*db, qs, batch, false, none);
-  return d.rq != nullptr && sweep_batch_scatter_ok(d, G);
-}
-
 int sp_query_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* db, int G) {
   return guarded([&] {
     scatter_group_check(qs, batch, db, G);
@@ -946,31 +854,18 @@ int sp_query_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t
     const size_t planes = db->params->p.planes();
     SweepBatchDesc d{};
     if (scatter_group_desc(qs, batch, db, G, d)) {
-      // ordered after every query's expansion (ev[1], recorded by sp_query_begin_for_db on the query's stream; the operand of
-      // the pass, qv, is written on that stream also when the odd subtree was split off) ...
-      Workspace& W0 = *qs[0]->ws;
-      for (int i = 1; i < batch; i++) HIP_CHECK(hipStreamWaitEvent(W0.stream, qs[i]->ws->ev[1], 0));
+      // ordered after every query's expansion (ev[1], recorded by sp_query_begin_for_db) ...
+      Workspace& W0 = group_pass_stream(qs, batch);
       sweep_batch_prepare(W0.D->T, d, W0.stream);
       launch_sweep_batch_scatter(W0.D->T, d, G, W0.stream);
-      HIP_CHECK(hipEventRecord(W0.ev[2], W0.stream));
       // ... and every query's own stream after the pass
-      for (int i = 1; i < batch; i++) {
-        Workspace& W = *qs[i]->ws;
-        HIP_CHECK(hipStreamWaitEvent(W.stream, W0.ev[2], 0));
-        HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
-      }
+      for (int i = 0; i < batch; i++) group_pass_done(qs, i);
     } else {
       // groups of 1 .. 3, rows that are not whole 32-row blocks, 8-byte databases, batch_mfma = 0: the per-query scatter sweep
       for (int i = 0; i < batch; i++) {
         Workspace& W = *qs[i]->ws;
-        W.out_G = G;
-        try {
-          for (size_t pl = 0; pl < planes; pl++) launch_plane_sweep(W, *db, pl);
-        } catch (...) {
-          W.out_G = 1;
-          throw;
-        }
-        W.out_G = 1;
+        ScatterLayout scatter(W, G);
+        for (size_t pl = 0; pl < planes; pl++) launch_plane_sweep(W, *db, pl);
         HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
       }
     }
@@ -985,9 +880,7 @@ int sp_query_fold_local(sp_query_t* q, const void* reduced_chunk, int G) {
   return guarded([&] {
     need(q && reduced_chunk, "null argument");
     need(q->state == 2, "sp_query_fold_local: sweep has not run");
-    const Params& p = q->params->p;
-    need(G >= 1 && (G & (G - 1)) == 0 && (size_t)G <= p.num_per() && G <= SP_MAX_ROW_SHARDS,
-         "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS)");
+    need_shard_count(q->params->p, G);
     run_fold_local(*q->ws, (const u32*)reduced_chunk, G);
     q->state = 4;
   });
@@ -996,8 +889,7 @@ int sp_query_fold_local_plane(sp_query_t* q, const void* reduced_plane_chunk, in
   return guarded([&] {
     need(q && reduced_plane_chunk, "null argument");
     const Params& p = q->params->p;
-    need(G >= 1 && (G & (G - 1)) == 0 && (size_t)G <= p.num_per() && G <= SP_MAX_ROW_SHARDS,
-         "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS)");
+    need_shard_count(p, G);
     need(plane >= 0 && (size_t)plane < p.planes(), "plane out of range");
     // plane `plane` must have been swept (its exchange is the caller's to order on sp_query_stream2)
     need((q->state == 1 && plane < q->next_plane) || q->state == 2, "sp_query_fold_local_plane: plane has not been swept");
@@ -1028,20 +920,8 @@ int sp_query_finish_gathered(sp_query_t* q, const void* gathered, int G, uint8_t
     need(q->state == 4, "sp_query_finish_gathered: local fold has not run");
     const Params& p = q->params->p;
     need(out_cap >= p.response_bytes(), "output buffer smaller than response_bytes");
-    Workspace& W = *q->ws;
-    run_finish_gathered(W, *q->pp, (const u64*)gathered, G);
-    HIP_CHECK(hipStreamSynchronize(W.stream));
-    memcpy(out, W.h_response, p.response_bytes());
-  *out_len = p.response_bytes();
-    float t = 0;
-    HIP_CHECK(hipEventElapsedTime(&t, W.ev[0], W.ev[1]));
-    q->ms[0] = t;
-    HIP_CHECK(hipEventElapsedTime(&t, W.ev[1], W.ev[2]));
-    q->ms[1] = t;
-    HIP_CHECK(hipEventElapsedTime(&t, W.ev[2], W.ev[3]));
-    q->ms[2] = t;
-    HIP_CHECK(hipEventElapsedTime(&t, W.ev[3], W.ev[4]));
-    q->ms[3] = t;
+    run_finish_gathered(*q->ws, *q->pp, (const u64*)gathered, G);
+    collect_response(q, out, out_len);
     q->state = 3;
   });
 }
@@ -1065,39 +945,6 @@ int sp_query_sync(sp_query_t* q) {
     HIP_CHECK(hipStreamSynchronize(q->ws->stream));
     HIP_CHECK(hipStreamSynchronize(q->ws->stream2));
   });
-}
-
-static void finish_impl(sp_query_t* q, bool premod, uint8_t* out, size_t out_cap, size_t* out_len) {
-  need(q && out && out_len, "null argument");
-  need(q->state == 2, "sp_query_finish: sweep has not run");
-  const Params& p = q->params->p;
-  need(out_cap >= p.response_bytes(), "output buffer smaller than response_bytes");
-  Workspace& W = *q->ws;
-  debug_stage(3);
-  run_finish(W, *q->pp, premod);
-  HIP_CHECK(hipStreamSynchronize(W.stream));
-  memcpy(out, W.h_response, p.response_bytes());
-  *out_len = p.response_bytes();
-  float t = 0;
-  HIP_CHECK(hipEventElapsedTime(&t, W.ev[0], W.ev[1]));
-  q->ms[0] = t;
-  HIP_CHECK(hipEventElapsedTime(&t, W.ev[1], W.ev[2]));
-  q->ms[1] = t;
-  HIP_CHECK(hipEventElapsedTime(&t, W.ev[2], W.ev[3]));
-  q->ms[2] = t;
-  HIP_CHECK(hipEventElapsedTime(&t, W.ev[3], W.ev[4]));
-  q->ms[3] = t;
-  if (W.have_sweep_span) {
-    // pipelined sweeps: [1] = first sweep launch begins -> last sweep launch done (on the stream that carries them),
-    // [2] = what is left of the span expanded -> folded (the exposed part of the last plane's fold)
-    float sw = 0, tot = 0;
-    HIP_CHECK(hipEventElapsedTime(&sw, W.ev_sw[0], W.ev_sw[1]));
-    HIP_CHECK(hipEventElapsedTime(&tot, W.ev[1], W.ev[3]));
-    q->ms[1] = sw;
-    q->ms[2] = tot > sw ? tot - sw : 0.f;
-    W.have_sweep_span = false;
-  }
-  q->state = 3;
 }
 
 int sp_query_finish(sp_query_t* q, uint8_t* out, size_t out_cap, size_t* out_len) {
@@ -1129,820 +976,12 @@ int sp_process_query(const sp_params_t* h, const sp_pp_t* pp, const uint8_t* que
   return rc;
 }
 
-int sp_process_query_batch(const sp_params_t* h, const sp_pp_t* const* pps, const uint8_t* const* queries,
-                           const size_t* query_lens, int batch, const sp_db_t* db, uint8_t* out, size_t out_stride,
-                           size_t* out_len) {
-  if (!h || !pps || !queries || !query_lens || batch < 0 || !db || !out || !out_len) {
-    g_last_error = "null argument";
-    return SP_E_ARG;
-  }
-  const Params& p = h->p;
-  tunables_new_call();  // the switches below are read before the first guarded() section of this call
-  // diagnostic (switch batch_trace): host time stamps of this call's phases on stderr, microseconds from entry
-  const bool trace = tunable("batch_trace", 0) != 0;
-  const auto t_entry = std::chrono::steady_clock::now();
-  auto stamp = [&](const char* what) {
-    if (trace)
-      fprintf(stderr, "[spiral] batch %-22s %8.1f us\n", what,
-              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_entry).count());
-  };
-  const bool batched = db->packed && db->num_shards == 1 && db->col_G == 1 && !tunable("no_batch_sweep", 0);
-  if (!batched) {
-    // 8-byte / narrow databases: one pass per query, up to `batch_in_flight` (default 3, at most 4; 1 = one at a time)
-    // queries in flight -- query i + 1 is deserialised, expanded and swept on its own workspace and streams before query
-    // i is waited for, so that its expansion, a chain of ~30 small dependent launches, runs under its predecessors' sweeps
-    // and folds instead of after them.  Lists of 8: C1 994 -> 1422 queries/s, P2 828 -> 1054.
-    if (db->num_shards != 1 || db->col_G != 1) {
-      g_last_error = "sp_process_query_batch needs an unsharded db";
-      return SP_E_ARG;
-    }
-    size_t depth = (size_t)std::max(1L, std::min(4L, tunable("batch_in_flight", 3)));
-    std::deque<std::pair<sp_query_t*, int>> flying;  // oldest first
-    int rc = SP_OK;
-    auto finish_oldest = [&]() -> int {
-      sp_query_t* q = flying.front().first;
-      const int qi = flying.front().second;
-      flying.pop_front();
-      int r = guarded([&] { finish_impl(q, false, out + (size_t)qi * out_stride, out_stride, out_len); });
-      sp_query_free(q);
-      return r;
-    };
-    for (int i = 0; i < batch && rc == SP_OK; i++) {
-      sp_query_t* q = sp_query_begin_for_db(h, pps[i], queries[i], query_lens[i], db);
-      if (!q && g_last_rc == SP_E_OOM && !flying.empty()) {
-        // no memory for one more workspace (sweep_out + fold buffers, up to ~2 GiB) beside the database and the queries in
-        // flight: finish those -- their workspaces return to the pool -- and go on one query at a time
-        while (rc == SP_OK && !flying.empty()) rc = finish_oldest();
-        if (rc != SP_OK) break;
-        depth = 1;
-        q = sp_query_begin_for_db(h, pps[i], queries[i], query_lens[i], db);
-      }
-      if (!q) {
-        rc = null_handle_rc();
-        break;
-      }
-      rc = sp_query_sweep(q, db);
-      if (rc != SP_OK) {
-        sp_query_free(q);
-        break;
-      }
-      flying.push_back({q, i});
-      while (rc == SP_OK && flying.size() >= depth) rc = finish_oldest();   // depth 1: one at a time
-    }
-    while (rc == SP_OK && !flying.empty()) rc = finish_oldest();
-    if (rc != SP_OK) {  // keep the first error; whatever is still in flight is drained and dropped
-      const std::string first = g_last_error;
-      for (auto& f : flying) {
-        (void)hipStreamSynchronize(f.first->ws->stream);
-        sp_query_free(f.first);
-      }
-      g_last_error = first;
-    }
-    return rc;
-  }
-  if (out_stride < p.response_bytes()) {
-    g_last_error = "out_stride smaller than response_bytes";
-    return SP_E_ARG;
-  }
-  // Groups of up to 8 queries -- 16 where the two-tile matrix-core pass applies (batch_group = 0, the default, asks the
-  // kernel side; a positive value caps the group) -- share one database pass.  Nothing waits for a group's folds before the next
-  // group's expansions and pass are queued (the passes themselves run one after the other: both are HBM-bound), and at
-  // most two groups hold workspaces at a time.  Measured at C2 (profiles/r02_fold_batch_experiments.md): the overlap
-  // buys nothing yet -- 16 queries take 2 x the time of 8, and 8 as 2 x 4 are slower (195 vs 236 queries/s) -- because
-  // the batched sweep's workgroups fill every CU's register file, so a fold wave only starts when the pass drains.
-  {  // the questions below (LDS opt-in limit, free memory) are put to the CURRENT device: it has to be the database's
-    const int rc0 = guarded([&] { check_device(db->device); });
-    if (rc0 != SP_OK) return rc0;
-  }
-  stamp("entry");
-  const int shape_max = sweep_batch_group_max(db->np_local, db->nj);
-  int group_max = (int)tunable("batch_group", 0);
-  if (group_max <= 0) group_max = shape_max;
-  group_max = std::max(1, std::min(shape_max, group_max));
-  if (group_max > SWEEP_BATCH_MAX && batch > SWEEP_BATCH_MAX) {
-    // two groups of 16 hold up to 32 workspaces: keep to groups of 8 when the device could not hold them beside the database
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < (size_t)2 * SWEEP_GROUP_MAX * group_ws_bytes(p, db->np_local))
-      group_max = SWEEP_BATCH_MAX;
-    (void)hipGetLastError();
-  }
-  stamp("group size decided");
-  // a list of exactly 9 .. 16 queries is one group; longer lists are cut into groups of group_max (a last group of <= 8
-  // takes the one-tile pass)
-  std::vector<sp_query_t*> all_qs;   // queries in flight (at most two groups: bounds the workspaces held)
-  size_t drained = 0;                // responses copied out so far
-  hipEvent_t prev_pass = nullptr;
-  auto drain = [&](size_t count) {   // oldest `count` queries: wait, copy the response out, give the workspace back
-    for (size_t i = 0; i < count; i++) {
-      Workspace& W = *all_qs[i]->ws;
-      HIP_CHECK(hipStreamSynchronize(W.stream));
-      memcpy(out + (drained + i) * out_stride, W.h_response, p.response_bytes());
-      *out_len = p.response_bytes();
-      // (run_finish joins the second stream into the main one before the response copy, and a split-off odd expansion subtree
-      // -- not used by grouped expansions -- is joined before the fold: both streams are idle now)
-      all_qs[i]->streams_idle = !W.right_pending;
-    }
-    for (size_t i = 0; i < count; i++) sp_query_free(all_qs[i]);
-    all_qs.erase(all_qs.begin(), all_qs.begin() + count);
-    drained += count;
-  };
-  size_t prev_group = 0;
-  int start = 0;   // first query not yet answered (a retry after an out-of-memory resumes here)
-  bool use_planar = true, one_group = false;   // what the out-of-memory ladder below gives up, in this order
-  auto run_groups = [&] {
-    check_device(db->device);
-    for (int g0 = start; g0 < batch; g0 += group_max) {
-      const int B = std::min(group_max, batch - g0);
-      if (one_group) {
-        if (!all_qs.empty()) drain(all_qs.size());                        // nothing in flight beside this group
-      } else if (all_qs.size() > prev_group) {
-        drain(all_qs.size() - prev_group);                                // keep only the previous group in flight
-      }
-      // 1. expand every query of the group on its own stream.  (r05: the sixteen expansions of a group are 8-10 of a step's 49 ms
-      // and looked like a launch-rate problem -- 1,600 small launches, 1.5 kernels in flight.  They are not: enqueued by 1, 2, 4 or
-      // 8 host threads, on 4, 8 or 16 hardware queues, or recorded and issued as ONE chain of ~100 table launches for the whole
-      // group, they take the same time -- 0.5 ms of a query's expansion is transforms that fill the chip (320 k forward NTTs, more
-      // than its fold has).  profiles/r05_batch16_step_timeline.md, r05_batch_expand.md; scripts/archive/r05_batch_expand/.)
-      // r06: they ARE 2x off the transform rate, and the cure is the shape of the launches, not their number: a round of ONE query
-      // under-fills the chip until its last rounds (a right-hand ciphertext's 57 transforms run in sequence in one workgroup), so
-      // the group's rounds are shared launches with the query as one more grid dimension (run_begin_group; switch expand_group).
-      const size_t first = all_qs.size();
-      const bool group_expand = B >= 2 && p.expand_queries && tunable("expand_group", 1) != 0;
-      for (int i = 0; i < B; i++) {
-        sp_query_t* q = group_expand ? query_open(h, pps[g0 + i]) : sp_query_begin(h, pps[g0 + i], queries[g0 + i], query_lens[g0 + i]);
-        if (!q) {
-          if (g_last_rc == SP_E_OOM) throw OomError(g_last_error);   // (reported by status: the caller retries in smaller groups)
-          throw ArgError(g_last_error);
-        }
-        all_qs.push_back(q);
-        q->ws->ensure_sweep();
-      }
-      sp_query_t* const* qs = all_qs.data() + first;
-      stamp("workspaces acquired");
-      if (group_expand) {
-        Workspace* Ws[GROUP_MAX];
-        for (int i = 0; i < B; i++) Ws[i] = qs[i]->ws.get();
-        run_begin_group(Ws, pps + g0, queries + g0, query_lens + g0, B);
-        for (int i = 0; i < B; i++) {
-          HIP_CHECK(hipEventRecord(Ws[i]->ev[1], Ws[i]->stream));
-          qs[i]->state = 1;
-        }
-      }
-      stamp("expansions enqueued");
-      // 2. one database pass for the whole group, on the first query's stream, after the previous group's pass; the first query
-      // holds the pass's pin of the planar copy
-      Workspace& W0 = *qs[0]->ws;
-      for (int i = 1; i < B; i++) HIP_CHECK(hipStreamWaitEvent(W0.stream, qs[i]->ws->ev[1], 0));
-      if (prev_pass) HIP_CHECK(hipStreamWaitEvent(W0.stream, prev_pass, 0));
-      SweepBatchDesc d = group_pass(*db, qs, B, use_planar, qs[0]->planar);
-      sweep_batch_prepare(W0.D->T, d, W0.stream);
-      // (a per-plane form of the pass with every query folding plane p beside the pass of plane p + 1 was measured in rounds
-      // 2 and 3 and is slower: the pass leaves no registers for a fold workgroup; profiles/r02_fold_batch_experiments.md)
-      launch_sweep_batch(W0.D->T, d, W0.stream);
-      HIP_CHECK(hipEventRecord(W0.ev[2], W0.stream));
-      prev_pass = W0.ev[2];
-      stamp("pass enqueued");
-      // 3. (rest of the) fold / pack per query, concurrently on the queries' own streams
-      for (int i = 0; i < B; i++) {
-        Workspace& W = *qs[i]->ws;
-        if (i > 0) {
-          HIP_CHECK(hipStreamWaitEvent(W.stream, W0.ev[2], 0));
-          HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
-        }
-        run_finish(W, *qs[i]->pp, false);
-      }
-      prev_group = (size_t)B;
-      stamp("folds enqueued");
-    }
-    drain(all_qs.size());
-    stamp("drained");
-  };
-  auto abandon = [&] {  // let whatever was queued drain before the workspaces go back to the pool
-    for (auto* q : all_qs) (void)hipStreamSynchronize(q->ws->stream);
-    for (auto* q : all_qs) sp_query_free(q);
-    all_qs.clear();
-    prev_group = 0;
-    prev_pass = nullptr;
-  };
-  int rc = guarded(run_groups);
-  // Out of memory (the hipMemGetInfo estimates above are rough): give up, one after the other, what only makes the call faster, and
-  // answer the REST of the list each time -- responses already copied out stay.  (1) the digit-planar copy of the database (its
-  // memory is released; a later call may build it again when there is room); (2) groups of 16 and the second group in flight:
-  // groups of 8, one at a time -- the in-flight queries' workspaces went back to the pool, so a group of 8 needs no more than was
-  // already allocated unless the failure came before 8 workspaces existed; (3) one query at a time, one workspace.
-  for (int step = 1; rc == SP_E_OOM && step <= 3; step++) {
-    abandon();
-    (void)hipGetLastError();
-    start = (int)drained;
-    if (step == 1) {   // (abandon has released the pins of the groups in flight: dropping the handle's copy frees it)
-      sp_db* wdb = const_cast<sp_db_t*>(db);
-      std::lock_guard<std::mutex> lk(wdb->mu);
-      use_planar = false;
-      if (!wdb->planar) continue;   // nothing to give back here: next step
-      wdb->drop_planar();
-      wdb->planar_state = -2;
-    } else if (step == 2) {
-      if (group_max <= SWEEP_BATCH_MAX && one_group) continue;
-      group_max = std::min(group_max, SWEEP_BATCH_MAX);
-      one_group = true;
-    } else {
-      rc = SP_OK;
-      for (int i = start; i < batch && rc == SP_OK; i++, drained++)
-        rc = sp_process_query(h, pps[i], queries[i], query_lens[i], db, out + (size_t)i * out_stride, out_stride, out_len);
-      break;
-    }
-    rc = guarded(run_groups);
-  }
-  if (rc != SP_OK) {
-    const std::string first_error = g_last_error;
-    abandon();
-    g_last_error = first_error;
-  }
-  for (auto* q : all_qs) sp_query_free(q);
-  return rc;
-}
-
-int sp_bench_sweep(sp_query_t* q, const sp_db_t* db, int iters, float* ms_per_launch) {
-  return sp_bench_sweep_ex(q, db, iters, -1, ms_per_launch);
-}
-
-int sp_bench_sweep_ex(sp_query_t* q, const sp_db_t* db, int iters, int per_plane_launches, float* ms_per_launch) {
-  return guarded([&] {
-    need(q && db && ms_per_launch && iters > 0, "bad argument");
-    need(q->state >= 1, "query not begun");
-    check_device(db->device);
-    Workspace& W = *q->ws;
-    TimingEvents ev;
-    // the same launches process_query issues for this database (one per plane when the sweep is pipelined)
-    const Params& p = q->params->p;
-    const bool per_plane = per_plane_launches < 0 ? sweep_is_pipelined(p, *db) : per_plane_launches != 0;
-    need(!per_plane || db->col_G == 1, "per-plane launches need a row-sharded or unsharded db");
-    auto sweep_once = [&] {
-      if (!per_plane) return run_sweep(W, *db);
-      W.ensure_sweep();
-      for (size_t pl = 0; pl < p.planes(); pl++) launch_plane_sweep(W, *db, pl);
-    };
-    sweep_once();  // warm
-    HIP_CHECK(hipEventRecord(ev.a, W.stream));
-    for (int i = 0; i < iters; i++) sweep_once();
-    HIP_CHECK(hipEventRecord(ev.b, W.stream));
-    HIP_CHECK(hipStreamSynchronize(W.stream));
-    float t = 0;
-    HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-    *ms_per_launch = t / ((float)iters * (per_plane ? (float)p.planes() : 1.0f));
-  });
-}
-
-int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, int iters, float* ms_per_pass) {
-  return guarded([&] {
-    need(qs && db && ms_per_pass && iters > 0 && batch >= 1 && batch <= sweep_batch_group_max(db ? db->np_local : 0, db ? db->nj : 0), "bad argument");
-    need(db->packed && db->num_shards == 1 && db->col_G == 1, "the batched pass needs an unsharded PACKED database");
-    check_device(db->device);
-    for (int i = 0; i < batch; i++) {
-      need(qs[i] && qs[i]->state >= 1, "query not begun");
-      need(qs[i]->params == db->params, "query and db were created for different params");
-    }
-    Workspace& W0 = *qs[0]->ws;
-    for (int i = 0; i < batch; i++) {
-      qs[i]->ws->ensure_sweep();
-      HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream));   // expansions done: the pass is timed alone
-      HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream2));
-    }
-    PlanarPin pin;   // held for the whole call: on every path out the pass's stream is synchronised before it is released
-    SweepBatchDesc d = group_pass(*db, qs, batch, true, pin);
-    struct Drain {
-      hipStream_t s;
-      ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{W0.stream};
-    TimingEvents ev;   // destroyed on every path out of here (launches and HIP_CHECK throw)
-    auto pass = [&] {
-      sweep_batch_prepare(W0.D->T, d, W0.stream);
-      launch_sweep_batch(W0.D->T, d, W0.stream);
-    };
-    pass();  // warm
-    HIP_CHECK(hipEventRecord(ev.a, W0.stream));
-    for (int i = 0; i < iters; i++) pass();
-    HIP_CHECK(hipEventRecord(ev.b, W0.stream));
-    HIP_CHECK(hipStreamSynchronize(W0.stream));
-    float t = 0;
-    HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-    *ms_per_pass = t / (float)iters;
-  });
-}
-
-int sp_bench_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* db, int G, int layout, int iters, float* ms_per_pass) {
-  return guarded([&] {
-    need(ms_per_pass && iters > 0 && (layout == 0 || layout == 1), "bad argument");
-    scatter_group_check(qs, batch, db, G);
-    for (int i = 0; i < batch; i++) {
-      need(qs[i]->state >= 1, "query not begun");
-      HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream));   // expansions done: the pass is timed alone
-      HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream2));
-    }
-    SweepBatchDesc d{};
-    need(scatter_group_desc(qs, batch, db, G, d), "this group / shard does not take the scatter-form pass (sp_query_sweep_scatter_group would sweep per query)");
-    Workspace& W0 = *qs[0]->ws;
-    struct Drain {
-      hipStream_t s;
-      ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{W0.stream};
-    TimingEvents ev;
-    auto pass = [&] {
-      sweep_batch_prepare(W0.D->T, d, W0.stream);
-      if (layout == 1)
-        launch_sweep_batch_scatter(W0.D->T, d, G, W0.stream);
-      else
-        launch_sweep_batch(W0.D->T, d, W0.stream);   // the same rows, plain [z][ii] output: the scatter form's lower bound
-    };
-    pass();  // warm
-    HIP_CHECK(hipEventRecord(ev.a, W0.stream));
-    for (int i = 0; i < iters; i++) pass();
-    HIP_CHECK(hipEventRecord(ev.b, W0.stream));
-    HIP_CHECK(hipStreamSynchronize(W0.stream));
-    float t = 0;
-    HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-    *ms_per_pass = t / (float)iters;
-  });
-}
-
-int sp_sweep_launches(const sp_params_t* h, const sp_db_t* db) {
-  if (!h || !db) return 0;
-  return sweep_is_pipelined(h->p, *db) ? (int)h->p.planes() : 1;
-}
-
-// Placement probe: launches `blocks` small workgroups on a stream whose CU mask has bits [bit_lo, bit_hi) set (the
-// whole device when bit_hi <= bit_lo) and reports the XCC / HW_ID registers each one saw.
-int sp_debug_cu_probe(int bit_lo, int bit_hi, int blocks, uint32_t* out2) {
-  return guarded([&] {
-    need(out2 && blocks > 0 && blocks <= 65536, "bad argument");
-    hipStream_t s = nullptr;
-    if (bit_hi > bit_lo) {
-      hipDeviceProp_t prop;
-      int dev = 0;
-      HIP_CHECK(hipGetDevice(&dev));
-      HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-      std::vector<uint32_t> m((prop.multiProcessorCount + 31) / 32, 0u);
-      for (int k = bit_lo; k < bit_hi && k < prop.multiProcessorCount; k++) m[k / 32] |= 1u << (k % 32);
-      HIP_CHECK(hipExtStreamCreateWithCUMask(&s, (uint32_t)m.size(), m.data()));
-    } else {
-      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    }
-    DevBuf<u32> d((size_t)blocks * 2);
-    launch_cu_probe(d.p, blocks, s);
-    HIP_CHECK(hipMemcpyAsync(out2, d.p, (size_t)blocks * 8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    (void)hipStreamDestroy(s);
-  });
-}
-
-// Resident-data check (diagnostic): for each of tw, neg1, gadget_gsw, lists, pp.all, pp.pack_cat -> 4 values:
-// checksum as a kernel on a fresh non-blocking stream sees it, checksum of a device-to-host copy, the kernel view again
-// after k_cache_sync (L2 write-back + invalidate on every XCD), and the checksum of the host original where the
-// library still has it (tw; 0 otherwise).  A kernel view that differs from the copy view is a stale cache line.
-int sp_debug_chacha20_u64(const uint8_t seed[32], uint64_t* out, size_t count) {
-  if (!seed || (!out && count)) {
-    g_last_error = "null argument";
-    return SP_E_ARG;
-  }
-  chacha20_keystream_u64(seed, out, count);
-  return SP_OK;
-}
-
-int sp_debug_resident_check(const sp_params_t* h, const sp_pp_t* pp, uint64_t* out, int cap) {
-  return guarded([&] {
-    need(h && pp && out && cap >= 24, "bad argument");
-    DeviceState& D = const_cast<sp_params*>(h)->device_state();
-    struct Item { const u32* p; size_t n; const u32* host; };
-    const Item items[6] = {{D.tw.p, D.tw.n, h->p.ntt_tables.data()}, {D.neg1.p, D.neg1.n, nullptr},
-                           {D.gadget_gsw.p, D.gadget_gsw.n, nullptr}, {(const u32*)D.lists.p, D.lists.n, nullptr},
-                           {pp->all.p, pp->all.n, nullptr}, {pp->pack_cat.p, pp->pack_cat.n, nullptr}};
-    hipStream_t s = nullptr;
-    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    DevBuf<unsigned long long> acc(12);
-    DevBuf<u32> sink(1);
-    auto host_sum = [](const u32* p, size_t n) {
-      unsigned long long a = 0;
-      for (size_t i = 0; i < n; i++) a += (unsigned long long)p[i] * (unsigned long long)((i << 1) | 1);
-      return a;
-    };
-    HIP_CHECK(hipMemsetAsync(acc.p, 0, 12 * 8, s));
-    for (int i = 0; i < 6; i++) launch_checksum(items[i].p, items[i].n, acc.p + i, s);
-    launch_cache_sync(sink.p, s);
-    for (int i = 0; i < 6; i++) launch_checksum(items[i].p, items[i].n, acc.p + 6 + i, s);
-    unsigned long long k[12];
-    HIP_CHECK(hipMemcpyAsync(k, acc.p, sizeof(k), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    for (int i = 0; i < 6; i++) {
-      std::vector<u32> hostcopy(items[i].n);
-      if (items[i].n) HIP_CHECK(hipMemcpy(hostcopy.data(), items[i].p, items[i].n * 4, hipMemcpyDeviceToHost));
-      out[4 * i + 0] = k[i];
-      out[4 * i + 1] = host_sum(hostcopy.data(), items[i].n);
-      out[4 * i + 2] = k[6 + i];
-      out[4 * i + 3] = items[i].host ? host_sum(items[i].host, items[i].n) : 0;
-    }
-    (void)hipStreamDestroy(s);
-  });
-}
-
-// transform-core micro-benchmark (profiling aid): ns per 2048-point forward NTT with M vectors per thread
-int sp_bench_ntt(const sp_params_t* h, int M, int blocks, int reps, float* ns_per_ntt) {
-  return guarded([&] {
-    need(h && ns_per_ntt && blocks > 0 && reps > 0, "bad argument");
-    Scoped W(h);
-    DevBuf<u32> scratch((size_t)blocks * 256);
-    const float ms = bench_ntt_core(W->D->T, M, blocks, reps, scratch.p, W->stream);
-    *ns_per_ntt = ms * 1e6f / ((float)blocks * reps * (M == 1 || M == 2 ? M : 4));
-  });
-}
-
-// ------------------------------------------------------------------------------- stage level
-int sp_to_ntt(const sp_params_t* h, const uint64_t* raw, uint64_t* out, size_t count) {
-  return guarded([&] {
-    need(h && raw && out, "null argument");
-    if (count == 0) return;
-    Scoped W(h);
-    DevBuf<u64> d_raw, tmp;
-    DevBuf<u32> d_ntt(count * 2 * POLY_LEN);
-    upload_raw(*W, raw, count * POLY_LEN, d_raw);
-    FwdDesc f{d_raw.p, nullptr, d_ntt.p, (int)count, 1, 1, 1, 64, 1, 0, 1};
-    launch_ntt_fwd(W->D->T, f, W->stream);
-    download_ntt(*W, d_ntt.p, count * 2 * POLY_LEN, out, tmp);
-  });
-}
-
-int sp_from_ntt(const sp_params_t* h, const uint64_t* ntt, uint64_t* out, size_t count) {
-  return guarded([&] {
-    need(h && ntt && out, "null argument");
-    if (count == 0) return;
-    Scoped W(h);
-    DevBuf<u64> tmp, d_raw(count * POLY_LEN);
-    DevBuf<u32> d_ntt;
-    upload_ntt(*W, ntt, count * 2 * POLY_LEN, d_ntt, tmp);
-    InvDesc inv{};
-    inv.src = d_ntt.p;
-    inv.poly_stride = 2 * POLY_LEN;
-    inv.crt_stride = POLY_LEN;
-    inv.z_stride = 1;
-    inv.dst = d_raw.p;
-    inv.n_polys = (int)count;
-    launch_ntt_inv(W->D->T, inv, W->stream);
-    download_raw(*W, d_raw.p, count * POLY_LEN, out);
-  });
-}
-
-int sp_ntt_forward(const sp_params_t* h, uint64_t* data, size_t count) {
-  return guarded([&] {
-    need(h && data, "null argument");
-    if (count == 0) return;
-    // each [crt] half is transformed under its own modulus: run the (value mod q_c -> NTT) kernel on
-    // every half and keep the matching modulus
-    std::vector<u64> full(count * 2 * 2 * POLY_LEN);
-    int rc = sp_to_ntt(h, data, full.data(), count * 2);
-    if (rc != SP_OK) throw HipError(g_last_error);
-    for (size_t i = 0; i < count; i++)
-      for (size_t c = 0; c < 2; c++)
-        memcpy(data + (i * 2 + c) * POLY_LEN, full.data() + ((i * 2 + c) * 2 + c) * POLY_LEN, POLY_LEN * 8);
-  });
-}
-
-int sp_ntt_inverse(const sp_params_t* h, uint64_t* data, size_t count) {
-  return guarded([&] {
-    need(h && data, "null argument");
-    if (count == 0) return;
-    // inverse both residues on the device; the per-modulus outputs are the residues of the composed value
-    std::vector<u64> raw(count * POLY_LEN);
-    int rc = sp_from_ntt(h, data, raw.data(), count);
-    if (rc != SP_OK) throw HipError(g_last_error);
-    for (size_t i = 0; i < count; i++)
-      for (size_t z = 0; z < POLY_LEN; z++) {
-        data[(i * 2 + 0) * POLY_LEN + z] = raw[i * POLY_LEN + z] % h->p.moduli[0];
-        data[(i * 2 + 1) * POLY_LEN + z] = raw[i * POLY_LEN + z] % h->p.moduli[1];
-      }
-  });
-}
-
-int sp_multiply(const sp_params_t* h, const uint64_t* a, size_t ar, size_t ac, const uint64_t* b, size_t bc,
-                uint64_t* res) {
-  return guarded([&] {
-    need(h && a && b && res && ar && ac && bc, "bad argument");
-    Scoped W(h);
-    DevBuf<u64> tmp;
-    DevBuf<u32> dA, dBt, dR(ar * bc * 2 * POLY_LEN);
-    upload_ntt(*W, a, ar * ac * 2 * POLY_LEN, dA, tmp);
-    // B is ac x bc; the MAC kernel wants the K operands of one output column contiguous: transpose on host
-    std::vector<u64> bt(ac * bc * 2 * POLY_LEN);
-    for (size_t k = 0; k < ac; k++)
-      for (size_t j = 0; j < bc; j++)
-        memcpy(bt.data() + (j * ac + k) * 2 * POLY_LEN, b + (k * bc + j) * 2 * POLY_LEN, 2 * POLY_LEN * 8);
-    DevBuf<u64> tmp2;
-    upload_ntt(*W, bt.data(), bt.size(), dBt, tmp2);
-    MacDesc m{};
-    m.A = dA.p;
-    m.B = dBt.p;
-    m.out = dR.p;
-    m.R = (int)ar;
-    m.K = (int)ac;
-    m.batch_inner = (int)bc;
-    m.batch_outer = 1;
-    m.B_inner_stride = (long)ac;
-    m.split_k = (int)ac;
-    m.out_batch_stride = 1;
-    m.out_row_stride = (int)bc;
-    launch_mac(W->D->T, m, W->stream);
-    download_ntt(*W, dR.p, ar * bc * 2 * POLY_LEN, res, tmp);
-  });
-}
-
-int sp_add(const sp_params_t* h, const uint64_t* a, const uint64_t* b, size_t count, uint64_t* res) {
-  return guarded([&] {
-    need(h && a && b && res && count, "bad argument");
-    Scoped W(h);
-    DevBuf<u64> tmp, tmp2;
-    DevBuf<u32> dA, dB, dR(count * 2 * POLY_LEN);
-    upload_ntt(*W, a, count * 2 * POLY_LEN, dA, tmp);
-    upload_ntt(*W, b, count * 2 * POLY_LEN, dB, tmp2);
-    launch_add(W->D->T, dR.p, dA.p, dB.p, (int)count, W->stream);
-    download_ntt(*W, dR.p, count * 2 * POLY_LEN, res, tmp);
-  });
-}
-int sp_add_into(const sp_params_t* h, uint64_t* res, const uint64_t* a, size_t count) {
-  return guarded([&] {
-    need(h && a && res && count, "bad argument");
-    Scoped W(h);
-    DevBuf<u64> tmp, tmp2;
-    DevBuf<u32> dA, dR;
-    upload_ntt(*W, res, count * 2 * POLY_LEN, dR, tmp);
-    upload_ntt(*W, a, count * 2 * POLY_LEN, dA, tmp2);
-    launch_add(W->D->T, dR.p, dR.p, dA.p, (int)count, W->stream);   // in place, as add_into (poly.rs:500-512)
-    download_ntt(*W, dR.p, count * 2 * POLY_LEN, res, tmp);
-  });
-}
-int sp_scalar_multiply(const sp_params_t* h, const uint64_t* scalar, const uint64_t* b, size_t count, uint64_t* res) {
-  return guarded([&] {
-    need(h && scalar && b && res && count, "bad argument");
-    Scoped W(h);
-    DevBuf<u64> tmp, tmp2;
-    DevBuf<u32> dS, dB(2 * count * 2 * POLY_LEN), dIn;
-    upload_ntt(*W, scalar, 2 * POLY_LEN, dS, tmp);
-    upload_ntt(*W, b, count * 2 * POLY_LEN, dIn, tmp2);
-    // the kernel the expansion uses (coefficient_expansion, server.rs:105-110): polys [count, 2 count) = scalar * polys [0, count)
-    launch_copy_words(dB.p, dIn.p, count * 2 * POLY_LEN, W->stream);
-    launch_scalar_mul(W->D->T, dB.p, (long)count, 0, dS.p, (int)count, W->stream);
-    download_ntt(*W, dB.p + count * 2 * POLY_LEN, count * 2 * POLY_LEN, res, tmp);
-  });
-}
-
-int sp_automorph(const sp_params_t* h, const uint64_t* a, size_t count, size_t t, uint64_t* res) {
-  return guarded([&] {
-    need(h && a && res && (t & 1), "bad argument (t must be odd)");
-    if (count == 0) return;
-    Scoped W(h);
-    DevBuf<u64> dA, dR(count * POLY_LEN);
-    upload_raw(*W, a, count * POLY_LEN, dA);
-    launch_automorph(W->D->T, dR.p, dA.p, (int)count, (int)t, W->stream);
-    download_raw(*W, dR.p, count * POLY_LEN, res);
-  });
-}
-
-int sp_gadget_invert_rdim(const sp_params_t* h, const uint64_t* inp, size_t rows_in, size_t cols, uint64_t* out,
-                          size_t rows_out, size_t rdim) {
-  return guarded([&] {
-    need(h && inp && out && rdim && rows_out % rdim == 0 && rdim <= rows_in, "bad argument");
-    Scoped W(h);
-    DevBuf<u64> dI, dO(rows_out * cols * POLY_LEN);
-    upload_raw(*W, inp, rows_in * cols * POLY_LEN, dI);
-    launch_gadget_raw(dO.p, dI.p, (int)rows_in, (int)cols, (int)rows_out, (int)rdim, (int)h->p.bits_per(rows_out / rdim), W->stream);
-    download_raw(*W, dO.p, rows_out * cols * POLY_LEN, out);
-  });
-}
-
-int sp_reorient_reg_ciphertexts(const sp_params_t* h, const uint64_t* v_reg, uint64_t* out) {
-  return guarded([&] {
-    need(h && v_reg && out, "null argument");
-    const Params& p = h->p;
-    Scoped W(h);
-    DevBuf<u64> tmp, dO(POLY_LEN * p.dim0() * 2);
-    DevBuf<u32> dV;
-    upload_ntt(*W, v_reg, p.dim0() * 2 * 2 * POLY_LEN, dV, tmp);
-    launch_reorient(dO.p, dV.p, 0, 1, (int)p.dim0(), W->stream);
-    download_raw(*W, dO.p, POLY_LEN * p.dim0() * 2, out);
-  });
-}
-
-int sp_multiply_reg_by_database(const sp_params_t* h, const uint64_t* db, const uint64_t* v_firstdim, size_t dim0,
-                                size_t num_per, uint64_t* out) {
-  return guarded([&] {
-    need(h && db && v_firstdim && out, "null argument");
-    need(dim0 >= 1 && num_per >= 1 && (num_per & (num_per - 1)) == 0 && num_per <= 65536 && dim0 <= 65536, "bad dimensions");
-    Scoped W(h);
-    const size_t words = POLY_LEN * num_per * dim0;
-    DevBuf<u64> d_ref(words), d_dev(words), d_q, d_out(num_per * 4 * POLY_LEN);
-    DevBuf<u32> d_res(4 * POLY_LEN * num_per);
-    HIP_CHECK(hipMemcpyAsync(d_ref.p, db, words * 8, hipMemcpyHostToDevice, W->stream));
-    const int packed = db_can_pack((int)num_per, (int)dim0) && !tunable("db_unpacked", 0) ? 1 : 0;
-    launch_db_relayout(d_dev.p, 0, d_ref.p, 0, N, (int)num_per, (int)dim0, 0, (int)dim0, packed, ColMap{}, W->stream);
-    upload_raw(*W, v_firstdim, POLY_LEN * dim0 * 2, d_q);
-    // the reference sums limb products in u128 and is exact for any limbs (server.rs:186-217); the sweep kernels sum up to 256
-    // products in u64 and need limbs < q: reduced here, as the loaders reduce the database words (same residues)
-    launch_canon_words(d_q.p, POLY_LEN * dim0 * 2, W->stream);
-    SweepDesc d{d_dev.p, d_q.p, d_res.p, 1, (int)num_per, (int)dim0, 0, (int)dim0, packed, 1};
-    launch_sweep(W->D->T, d, W->stream);
-    launch_sweep_out_to_ref(d_out.p, d_res.p, (int)num_per, W->stream);
-    download_raw(*W, d_out.p, num_per * 4 * POLY_LEN, out);
-  });
-}
-
-int sp_coefficient_expansion(const sp_params_t* h, const sp_pp_t* pp, uint64_t* v, size_t g, size_t stop_round,
-                             size_t max_bits_to_gen_right) {
-  return guarded([&] {
-    need(h && pp && v, "null argument");
-    const Params& p = h->p;
-    need(p.expand_queries, "params have no query expansion");
-    // the schedule (pruning) is derived from params exactly as expand_query derives it (server.rs:536-564)
-    const size_t sr = p.db_dim_2 > 0 ? p.stop_round() : 0, mb = p.db_dim_2 > 0 ? p.t_gsw * p.db_dim_2 : 0;
-    need(g == p.g() && stop_round == sr && max_bits_to_gen_right == mb, "g / stop_round / max_bits_to_gen_right must match params");
-    check_device(pp->device);
-    Scoped W(h);
-    W->ensure_expand();
-    const size_t words = ((size_t)1 << g) * 2 * 2 * POLY_LEN;
-    DevBuf<u64> tmp;
-    tmp.ensure(words);
-    HIP_CHECK(hipMemcpyAsync(tmp.p, v, words * 8, hipMemcpyHostToDevice, W->stream));
-    launch_u64_to_u32(W->v.p, tmp.p, (long)words, W->stream);
-    run_coefficient_expansion(*W, *pp, g);
-    download_ntt(*W, W->v.p, words, v, tmp);
-  });
-}
-
-int sp_regev_to_gsw(const sp_params_t* h, const sp_pp_t* pp, const uint64_t* v_inp, uint64_t* v_gsw, size_t num_gsw) {
-  return guarded([&] {
-    need(h && pp && v_inp && v_gsw, "null argument");
-    const Params& p = h->p;
-    need(num_gsw == p.db_dim_2 && num_gsw > 0, "num_gsw must equal nu_2");
-    check_device(pp->device);
-    Scoped W(h);
-    W->ensure_expand();
-    const size_t nb = num_gsw * p.t_gsw;
-    DevBuf<u64> tmp;
-    DevBuf<u32> dV;
-    upload_ntt(*W, v_inp, nb * 2 * 2 * POLY_LEN, dV, tmp);
-    std::vector<int> ct(nb), poly(nb);
-    for (size_t b = 0; b < nb; b++) {
-      ct[b] = (int)b;
-      poly[b] = (int)(2 * b);
-    }
-    DevBuf<int> dl(2 * nb);
-    HIP_CHECK(hipMemcpyAsync(dl.p, ct.data(), nb * sizeof(int), hipMemcpyHostToDevice, W->stream));
-    HIP_CHECK(hipMemcpyAsync(dl.p + nb, poly.data(), nb * sizeof(int), hipMemcpyHostToDevice, W->stream));
-    run_regev_to_gsw(*W, *pp, dV.p, dl.p, dl.p + nb);
-    // gather the right halves (2 x 2t_gsw per GSW ct)
-    const size_t two_t = 2 * p.t_gsw;
-    DevBuf<u32> dense(num_gsw * 2 * two_t * 2 * POLY_LEN);
-    for (size_t d = 0; d < num_gsw; d++)
-      for (size_t r = 0; r < 2; r++)
-        HIP_CHECK(hipMemcpyAsync(dense.p + ((d * 2 + r) * two_t) * 2 * POLY_LEN,
-                                 W->fold_mats.p + ((d * 2 + r) * 2 * two_t + two_t) * 2 * POLY_LEN,
-                                 two_t * 2 * POLY_LEN * sizeof(u32), hipMemcpyDeviceToDevice, W->stream));
-    download_ntt(*W, dense.p, num_gsw * 2 * two_t * 2 * POLY_LEN, v_gsw, tmp);
-  });
-}
-
-int sp_get_v_folding_neg(const sp_params_t* h, const uint64_t* v_folding, uint64_t* out) {
-  return guarded([&] {
-    need(h && v_folding && out, "null argument");
-    const Params& p = h->p;
-    const size_t nu2 = p.db_dim_2, two_t = 2 * p.t_gsw;
-    if (nu2 == 0) return;
-    Scoped W(h);
-    W->ensure_expand();
-    DevBuf<u64> tmp;
-    DevBuf<u32> dense;
-    upload_ntt(*W, v_folding, nu2 * 2 * two_t * 2 * POLY_LEN, dense, tmp);
-    for (size_t d = 0; d < nu2; d++)
-      for (size_t r = 0; r < 2; r++)
-        HIP_CHECK(hipMemcpyAsync(W->fold_mats.p + ((d * 2 + r) * 2 * two_t + two_t) * 2 * POLY_LEN,
-                                 dense.p + ((d * 2 + r) * two_t) * 2 * POLY_LEN, two_t * 2 * POLY_LEN * sizeof(u32),
-                                 hipMemcpyDeviceToDevice, W->stream));
-    run_folding_neg(*W);
-    for (size_t d = 0; d < nu2; d++)
-      for (size_t r = 0; r < 2; r++)
-        HIP_CHECK(hipMemcpyAsync(dense.p + ((d * 2 + r) * two_t) * 2 * POLY_LEN,
-                                 W->fold_mats.p + ((d * 2 + r) * 2 * two_t) * 2 * POLY_LEN,
-                                 two_t * 2 * POLY_LEN * sizeof(u32), hipMemcpyDeviceToDevice, W->stream));
-    download_ntt(*W, dense.p, nu2 * 2 * two_t * 2 * POLY_LEN, out, tmp);
-  });
-}
-
-int sp_expand_query(const sp_params_t* h, const sp_pp_t* pp, const uint8_t* query, size_t query_len,
-                    uint64_t* v_reg_reoriented, uint64_t* v_folding) {
-  return guarded([&] {
-    need(h && pp && query && v_reg_reoriented, "null argument");
-    const Params& p = h->p;
-    check_device(pp->device);
-    Scoped W(h);
-    run_begin(*W, *pp, query, query_len);
-    join_right(*W);  // the GSW side is produced on the second stream
-    download_raw(*W, W->qv.p, POLY_LEN * p.dim0() * 2, v_reg_reoriented);
-    const size_t nu2 = p.db_dim_2, two_t = 2 * p.t_gsw;
-    if (nu2 > 0) {
-      need(v_folding != nullptr, "v_folding is null");
-      DevBuf<u32> dense(nu2 * 2 * two_t * 2 * POLY_LEN);
-      for (size_t d = 0; d < nu2; d++)
-        for (size_t r = 0; r < 2; r++)
-          HIP_CHECK(hipMemcpyAsync(dense.p + ((d * 2 + r) * two_t) * 2 * POLY_LEN,
-                                   W->fold_mats.p + ((d * 2 + r) * 2 * two_t + two_t) * 2 * POLY_LEN,
-                                   two_t * 2 * POLY_LEN * sizeof(u32), hipMemcpyDeviceToDevice, W->stream));
-      DevBuf<u64> tmp;
-      download_ntt(*W, dense.p, nu2 * 2 * two_t * 2 * POLY_LEN, v_folding, tmp);
-    }
-  });
-}
-
-int sp_fold_ciphertexts(const sp_params_t* h, uint64_t* cts, size_t num_per, const uint64_t* v_folding,
-                        const uint64_t* v_folding_neg) {
-  return guarded([&] {
-    need(h && cts && v_folding && v_folding_neg, "null argument");
-    const Params& p = h->p;
-    need(num_per >= 1 && (num_per & (num_per - 1)) == 0, "num_per must be a power of two");
-    size_t further = 0;
-    while (((size_t)1 << further) < num_per) further++;
-    if (further == 0) return;
-    const size_t two_t = 2 * p.t_gsw;
-    Scoped W(h);
-    ensure_stage_fold(*W, num_per, further);
-    DevBuf<u64> tmp;
-    DevBuf<u32> dF, dFn;
-    upload_ntt(*W, v_folding, further * 2 * two_t * 2 * POLY_LEN, dF, tmp);
-    DevBuf<u64> tmp2;
-    upload_ntt(*W, v_folding_neg, further * 2 * two_t * 2 * POLY_LEN, dFn, tmp2);
-    for (size_t d = 0; d < further; d++)
-      for (size_t r = 0; r < 2; r++) {
-        u32* row = W->fold_mats.p + ((d * 2 + r) * 2 * two_t) * 2 * POLY_LEN;
-        HIP_CHECK(hipMemcpyAsync(row, dFn.p + ((d * 2 + r) * two_t) * 2 * POLY_LEN, two_t * 2 * POLY_LEN * sizeof(u32), hipMemcpyDeviceToDevice, W->stream));
-        HIP_CHECK(hipMemcpyAsync(row + two_t * 2 * POLY_LEN, dF.p + ((d * 2 + r) * two_t) * 2 * POLY_LEN, two_t * 2 * POLY_LEN * sizeof(u32), hipMemcpyDeviceToDevice, W->stream));
-      }
-    HIP_CHECK(hipMemcpyAsync(W->foldX.p, cts, num_per * 2 * POLY_LEN * 8, hipMemcpyHostToDevice, W->stream));
-    W->mats_w_ready = false;   // (whatever wave-layout operands the pooled workspace holds are not this call's)
-    // the stage export honours the caller's v_folding_neg: literal path, every digit
-    u64* res = run_fold(*W, FoldOpts{1L << 60, false, false}, W->foldX.p, W->foldY.p, 1, (int)num_per, -1);
-    download_raw(*W, res, 2 * POLY_LEN, cts);
-  });
-}
-
-int sp_fold_ciphertexts_fused(const sp_params_t* h, uint64_t* cts, size_t num_per, const uint64_t* v_folding,
-                              long fused_min_pairs) {
-  return guarded([&] {
-    need(h && cts && v_folding, "null argument");
-    const Params& p = h->p;
-    need(num_per >= 1 && (num_per & (num_per - 1)) == 0, "num_per must be a power of two");
-    size_t further = 0;
-    while (((size_t)1 << further) < num_per) further++;
-    if (further == 0) return;
-    const size_t two_t = 2 * p.t_gsw;
-    Scoped W(h);
-    ensure_stage_fold(*W, num_per, further);
-    DevBuf<u64> tmp;
-    DevBuf<u32> dF;
-    upload_ntt(*W, v_folding, further * 2 * two_t * 2 * POLY_LEN, dF, tmp);
-    for (size_t d = 0; d < further; d++)
-      for (size_t r = 0; r < 2; r++) {
-        u32* row = W->fold_mats.p + ((d * 2 + r) * 2 * two_t) * 2 * POLY_LEN;
-        HIP_CHECK(hipMemcpyAsync(row + two_t * 2 * POLY_LEN, dF.p + ((d * 2 + r) * two_t) * 2 * POLY_LEN, two_t * 2 * POLY_LEN * sizeof(u32), hipMemcpyDeviceToDevice, W->stream));
-      }
-    launch_folding_neg(W->D->T, W->fold_mats.p, W->D->gadget_gsw.p, (int)further, (int)two_t, W->stream);
-    run_mats_to_wave(*W, further);
-    HIP_CHECK(hipMemcpyAsync(W->foldX.p, cts, num_per * 2 * POLY_LEN * 8, hipMemcpyHostToDevice, W->stream));
-    // the caller's ciphertexts: below Q (what the reference's invariants give, and what lets the kernels skip the dead top
-    // digit) only if every coefficient says so -- checked here, on the host copy
-    bool below_q = true;
-    for (size_t i = 0; i < num_per * 2 * POLY_LEN && below_q; i++) below_q = cts[i] < p.modulus;
-    const FoldOpts o{fused_min_pairs > 0 ? fused_min_pairs : W->fused_min_pairs, true, below_q};
-    u64* res = run_fold(*W, o, W->foldX.p, W->foldY.p, 1, (int)num_per, -1);
-    download_raw(*W, res, 2 * POLY_LEN, cts);
-  });
-}
-
-int sp_pack(const sp_params_t* h, const sp_pp_t* pp, const uint64_t* v_ct, uint64_t* out) {
-  return guarded([&] {
-    need(h && pp && v_ct && out, "null argument");
-    const Params& p = h->p;
-    need(p.instances == 1, "sp_pack packs one instance (n*n cts); call per instance");
-    check_device(pp->device);
-    Scoped W(h);
-    W->ensure_finish();
-    HIP_CHECK(hipMemcpyAsync(W->final_cts.p, v_ct, p.n * p.n * 2 * POLY_LEN * 8, hipMemcpyHostToDevice, W->stream));
-    run_pack(*W, *pp);
-    DevBuf<u64> tmp;
-    download_ntt(*W, W->pack_res.p, (p.n + 1) * p.n * 2 * POLY_LEN, out, tmp);
-  });
-}
-
-int sp_encode(const sp_params_t* h, const uint64_t* v_packed, uint8_t* out, size_t out_cap, size_t* out_len) {
-  return guarded([&] {
-    need(h && v_packed && out && out_len, "null argument");
-    need(out_cap >= h->p.response_bytes(), "output buffer smaller than response_bytes");
-    *out_len = encode_response(h->p, v_packed, out);
-  });
-}
-
 }  // extern "C"
+
+// The build lists of this tree (Makefile, tests/emu/build_emulated_library.py) compile capi_batch.cpp and capi_stage.cpp as
+// translation units of their own and say so with SPIRAL_CAPI_SPLIT.  A list that names capi.cpp alone, as every list did before the
+// file was split, still builds the whole surface.
+#ifndef SPIRAL_CAPI_SPLIT
+#include "capi_batch.cpp"
+#include "capi_stage.cpp"
+#endif

@@ -270,6 +270,27 @@ struct ShardedRun {
   hipStream_t main = nullptr;
   size_t planes = 0, local_words = 0;
 };
+void need_own_device(const sp_comm_t* c) {
+  int dev = 0;
+  hip_ok(hipGetDevice(&dev), "hipGetDevice");
+  if (dev != c->device) throw Fail{SP_E_ARG, "the communicator was created on another HIP device"};
+}
+// comm_reserve sized `mine` / `gathered` from the parameters alone; `words` is the partial layout a query really produced, B
+// queries share the buffers.  A disagreement (a future output layout, a column shard) must fail here, not write past `mine`.
+void need_reserved(const sp_comm_t* c, size_t B, size_t words, size_t planes, size_t local_words, const char* msg) {
+  const size_t G = (size_t)c->world, pw = words / planes, chunk = pw / G;
+  if (words % planes != 0 || pw % G != 0 || B * planes * chunk * sizeof(uint32_t) > c->mine_bytes ||
+      B * G * local_words * sizeof(uint64_t) > c->gathered_bytes)
+    throw Fail{SP_E_ARG, msg};
+}
+// the timings of the (last) query of a per-query flow
+void read_stage_ms(sp_comm_t* c) {
+  // [0] sweep launches incl. the exchanges overlapped with them, [1] exchange tail + local fold + all-gather
+  (void)hipEventElapsedTime(&c->ms[0], c->ev_t[0], c->ev_t[1]);
+  (void)hipEventElapsedTime(&c->ms[1], c->ev_t[1], c->ev_t[2]);
+  // [2] what of the exchange is NOT hidden behind the sweeps: last sweep launch done -> last plane's reduce-scatter done
+  if (hipEventElapsedTime(&c->ms[2], c->ev_t[1], c->ev_rs) != hipSuccess || c->ms[2] < 0) c->ms[2] = 0;
+}
 // on_critical_path: nothing of this rank's runs beside the expansion (a single query, the first of a list) -- then its odd subtree
 // and GSW side may move beside the sweeps that follow (capi.cpp, expand_split_shards); a list's later queries expand under their
 // predecessor's sweeps and keep the one-stream form
@@ -289,11 +310,7 @@ void sharded_sweeps(sp_comm_t* c, const sp_db_t* shard, ShardedRun& r, bool time
   uint32_t* part = (uint32_t*)sp_query_partial_ptr(r.q);
   if (!part) throw Fail{SP_E_OOM, std::string("partial buffer: ") + sp_last_error()};
   const size_t words = sp_query_partial_words(r.q), pw = words / r.planes, chunk = pw / (size_t)G;
-  // comm_reserve sized `mine` / `gathered` from the parameters alone; this is the partial layout the query really produced.
-  // A disagreement (a future output layout, a column shard) must fail here, not write past `mine`.
-  if (words % r.planes != 0 || pw % (size_t)G != 0 || r.planes * chunk * sizeof(uint32_t) > c->mine_bytes ||
-      (size_t)G * r.local_words * sizeof(uint64_t) > c->gathered_bytes)
-    throw Fail{SP_E_ARG, "internal: the query's partial buffer does not match the reserved exchange buffers"};
+  need_reserved(c, 1, words, r.planes, r.local_words, "internal: the query's partial buffer does not match the reserved exchange buffers");
   if (timed) hip_ok(hipEventRecord(c->ev_t[0], r.main), "hipEventRecord");
   for (size_t pl = 0; pl < r.planes; pl++) {
     sp_ok(sp_query_sweep_scatter_plane(r.q, shard, G, (int)pl), "sp_query_sweep_scatter_plane");
@@ -347,18 +364,12 @@ int sp_process_query_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t* 
   std::lock_guard<std::mutex> lk(c->mu);
   ShardedRun r;
   int rc = guarded_comm([&] {
-    int dev = 0;
-    hip_ok(hipGetDevice(&dev), "hipGetDevice");
-    if (dev != c->device) throw Fail{SP_E_ARG, "the communicator was created on another HIP device"};
+    need_own_device(c);
     comm_reserve(c, h);   // no-op after sp_comm_reserve / the first query with these params
     sharded_begin(c, h, pp, query, query_len, shard, r, true);
     sharded_sweeps(c, shard, r, true);
     sharded_finish(c, r, out, out_cap, out_len, true);
-    // [0] sweep launches incl. the exchanges overlapped with them, [1] exchange tail + local fold + all-gather
-    (void)hipEventElapsedTime(&c->ms[0], c->ev_t[0], c->ev_t[1]);
-    (void)hipEventElapsedTime(&c->ms[1], c->ev_t[1], c->ev_t[2]);
-    // [2] what of the exchange is NOT hidden behind the sweeps: last sweep launch done -> last plane's reduce-scatter done
-    if (hipEventElapsedTime(&c->ms[2], c->ev_t[1], c->ev_rs) != hipSuccess || c->ms[2] < 0) c->ms[2] = 0;
+    read_stage_ms(c);
     note_transport(c);
   });
   if (r.q) {
@@ -377,9 +388,7 @@ static int queries_sharded_locked(sp_comm_t* c, const sp_params_t* h, const sp_p
                                   size_t* out_len) {
   ShardedRun cur, nxt;
   int rc = guarded_comm([&] {
-    int dev = 0;
-    hip_ok(hipGetDevice(&dev), "hipGetDevice");
-    if (dev != c->device) throw Fail{SP_E_ARG, "the communicator was created on another HIP device"};
+    need_own_device(c);
     *out_len = 0;
     if (n == 0) return;
     comm_reserve(c, h);
@@ -396,9 +405,7 @@ static int queries_sharded_locked(sp_comm_t* c, const sp_params_t* h, const sp_p
       nxt = ShardedRun{};
     }
     cur = ShardedRun{};
-    (void)hipEventElapsedTime(&c->ms[0], c->ev_t[0], c->ev_t[1]);
-    (void)hipEventElapsedTime(&c->ms[1], c->ev_t[1], c->ev_t[2]);
-    if (hipEventElapsedTime(&c->ms[2], c->ev_t[1], c->ev_rs) != hipSuccess || c->ms[2] < 0) c->ms[2] = 0;
+    read_stage_ms(c);
     note_transport(c);
     c->last_group = 1;
     c->last_reduce_scatters = (size_t)n * c->planes_last;
@@ -471,9 +478,7 @@ int sp_process_queries_sharded_batched(sp_comm_t* c, const sp_params_t* h, const
     for (int i = 0; i < B; i++) sharded_begin(c, h, pps[first + i], queries[first + i], query_lens[first + i], shard, v[i], false);
   };
   int rc = guarded_comm([&] {
-    int dev = 0;
-    hip_ok(hipGetDevice(&dev), "hipGetDevice");
-    if (dev != c->device) throw Fail{SP_E_ARG, "the communicator was created on another HIP device"};
+    need_own_device(c);
     *out_len = 0;
     comm_reserve(c, h, group);   // no-op after sp_comm_reserve_batch / the first list with these params and this group
     size_t n_rs = 0, n_ag = 0;
@@ -485,9 +490,7 @@ int sp_process_queries_sharded_batched(sp_comm_t* c, const sp_params_t* h, const
       for (int i = 0; i < B; i++) qs[i] = cur[i].q;
       sp_ok(sp_query_sweep_scatter_group(qs, B, shard, G), "sp_query_sweep_scatter_group");
       const size_t words = sp_query_partial_words(qs[0]), pw = words / planes, chunk = pw / (size_t)G;
-      if (words % planes != 0 || pw % (size_t)G != 0 || (size_t)B * planes * chunk * sizeof(uint32_t) > c->mine_bytes ||
-          (size_t)B * G * local_words * sizeof(uint64_t) > c->gathered_bytes)
-        throw Fail{SP_E_ARG, "internal: the queries' partial buffers do not match the reserved exchange buffers"};
+      need_reserved(c, (size_t)B, words, planes, local_words, "internal: the queries' partial buffers do not match the reserved exchange buffers");
       for (int i = 0; i < B; i++) {
         uint32_t* part = (uint32_t*)sp_query_partial_ptr(qs[i]);
         if (!part) throw Fail{SP_E_OOM, std::string("partial buffer: ") + sp_last_error()};

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE (run by tests/test_emulated_library.py in a child process with SPIRAL_HIP_LIB = the emulated build): the
-out-of-memory ladder of sp_process_query_batch (capi.cpp), driven by the emulator's device-memory budget
+out-of-memory ladder of sp_process_query_batch (capi_batch.cpp), driven by the emulator's device-memory budget
 (tests/emu/emu_streams.cpp: hipMalloc fails once the live device bytes would exceed it).
 
 A list of nine queries against a PACKED 64 x 128 database with its digit-planar copy built, three times, every response against

@@ -137,7 +137,7 @@ def test_group_expansion_on_the_emulated_device(emulated):
 
 @pytest.mark.parametrize("case", ["A", pytest.param("B", marks=long_only), pytest.param("C", marks=long_only)])
 def test_out_of_memory_ladder_of_the_batched_call(emulated, case):
-    """sp_process_query_batch when device memory runs out inside a group (capi.cpp): the emulator's device-memory
+    """sp_process_query_batch when device memory runs out inside a group (capi_batch.cpp): the emulator's device-memory
     budget makes hipMalloc fail at a chosen point (tests/_emu_oom_ladder.py).  A: the digit-planar copy is given back and the list
     runs through the PACKED two-tile kernel; B: groups of 8, one at a time; C: one query at a time.  Every response == oracle.
     (Case A is also the default suite's run of a batched group's SHARED expansion launches -- eleven queries, path bit asserted;
@@ -145,6 +145,26 @@ def test_out_of_memory_ladder_of_the_batched_call(emulated, case):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_emu_oom_ladder.py"), case], cwd=ROOT,
                        env=dict(os.environ, SPIRAL_HIP_LIB=emulated), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0 and "oom-ladder-ok" in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
+def test_failed_scatter_sweep_leaves_no_layout_in_the_pool(emulated):
+    """sp_query_sweep_scatter switches its workspace to the reduce-scatter output layout for the sweep's launches.  When the sweep
+    throws (here: the emulator's device-memory budget fails the output buffer's allocation, ws_prealloc = 0) the workspace must be
+    back in the plain layout before it returns to the pool: the next sp_process_query with the same params == oracle
+    (tests/_emu_scatter_layout.py)."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_emu_scatter_layout.py")], cwd=ROOT,
+                       env=dict(os.environ, SPIRAL_HIP_LIB=emulated), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "scatter-layout-ok" in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
+def test_capi_alone_still_holds_the_whole_surface(emulated):
+    """Both build lists compile capi.cpp's parts (capi_batch.cpp, capi_stage.cpp) separately and say so with SPIRAL_CAPI_SPLIT; a
+    list that names capi.cpp alone gets them through the includes at its end.  That path is compiled nowhere else: it must parse."""
+    flags = [f for f in emu_build.FLAGS if f != "-DSPIRAL_CAPI_SPLIT"]
+    assert len(flags) == len(emu_build.FLAGS) - 1
+    r = subprocess.run([emu_build.CLANG, "-x", "c++"] + flags + ["-fsyntax-only", os.path.join(emu_build.CSRC, "capi.cpp")],
+                       capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-3000:]
 
 
 @long_only
