@@ -10,6 +10,7 @@ using namespace spiral;
 static thread_local std::string g_last_error;
 static thread_local int g_last_rc = SP_OK;  // status of this thread's last guarded() section: what a constructor-style entry
                                              // point (returns a handle or null) failed with
+static thread_local int g_shard_split_hint = 1;   // 0 while a list of sharded queries is being enqueued
 int spiral::guarded_status(int rc, const char* what) {
   if (rc != SP_OK) g_last_error = what;
   g_last_rc = rc;
@@ -108,6 +109,18 @@ void spiral::group_pass_done(sp_query_t* const* qs, int i) {
   HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
 }
 
+void spiral::sparse_group_pass(const sp_db& db, sp_query_t* const* qs, int B, hipStream_t s) {
+  need(B >= 1 && B <= SPARSE_GROUP_MAX, "a sparse bucket's pass takes 1 .. 8 queries");
+  Workspace* Ws[SPARSE_GROUP_MAX];
+  for (int i = 0; i < B; i++) {
+    need(qs[i] && qs[i]->for_sparse == &db && qs[i]->sparse_index == qs[0]->sparse_index,
+         "the queries of a sparse bucket's group must have been begun on one snapshot of its index");
+    Ws[i] = qs[i]->ws.get();
+  }
+  const sp_db::SparseIndex& idx = *qs[0]->sparse_index;
+  run_sweep_sparse_group(Ws, B, db, idx.col_ptr.p, idx.col_rows.p, idx.col_slots.p, s);
+}
+
 // The digit-planar copy of a PACKED, unsharded database (sweep_planar.hpp): what the 9 .. 16-query pass reads.  Built by
 // sp_db_prepare_batch (at load time) or on first use (one gather pass over the PACKED units), only when the device has the room for
 // a second copy (8 bytes per word) beside the workspaces of two groups; null = keep to the PACKED kernels.
@@ -187,13 +200,14 @@ std::shared_ptr<const sp_db::SparseIndex> sp_db::ensure_sparse_index() {
 // ---- pieces of the query stage machine (below) that are not entry points themselves
 // the head of every query: the handles checked, a sparse bucket's index snapshot taken, the workspace acquired and the "begin" event
 // recorded; state 0
-static std::unique_ptr<sp_query> open_query(const sp_params_t* h, const sp_pp_t* pp, const sp_db_t* db) {
+static std::unique_ptr<sp_query> open_query(const sp_params_t* h, const sp_pp_t* pp, const sp_db_t* db,
+                                            std::shared_ptr<const sp_db::SparseIndex> snapshot = nullptr) {
   need(h && pp, "null argument");
   need(pp->params == h, "public parameters were created for different params");
   need(!db || db->params == h, "db was created for different params");
   check_device(pp->device);
   auto q = std::make_unique<sp_query>();
-  if (db && db->sparse) q->sparse_index = const_cast<sp_db*>(db)->ensure_sparse_index();
+  if (db && db->sparse) q->sparse_index = snapshot ? std::move(snapshot) : const_cast<sp_db*>(db)->ensure_sparse_index();
   q->params = const_cast<sp_params*>(h);
   q->pp = pp;
   q->ws = q->params->acquire_ws();
@@ -202,6 +216,49 @@ static std::unique_ptr<sp_query> open_query(const sp_params_t* h, const sp_pp_t*
 }
 sp_query_t* spiral::query_open(const sp_params_t* h, const sp_pp_t* pp) {
   return guarded_handle([&] { return open_query(h, pp, nullptr); });
+}
+
+// the rest of sp_query_begin_for_db once the query is open: the expansion (pruned to a row shard's rows or to a sparse bucket's
+// occupied rows, the snapshot the query holds) enqueued on the query's stream, ev[1] recorded; state 1
+static void begin_opened(sp_query* q, const uint8_t* query, size_t query_len, const sp_db_t* db) {
+  const sp_params* h = q->params;
+  const sp_pp* pp = q->pp;
+  Workspace& W = *q->ws;
+  const bool rows = db && db->num_shards > 1 && db->col_G == 1;
+  const DeviceState::PrunedPlan* plan = q->sparse_index ? q->sparse_index->plan.get() : nullptr;
+  // a long (per-plane, pipelined) sweep follows: worth moving the fold's half of the expansion off the critical path
+  // (r06: also before the per-plane sweeps of a ROW SHARD -- the multi-GPU flows: the even subtree, pruned to the shard's rows,
+  // is short there, and the odd subtree + GSW side, which only the fold needs, then runs beside the sweeps and their exchanges
+  // instead of in front of them; switch expand_split_shards)
+  // NOT for a LIST of sharded queries (sp_process_queries_sharded): query k + 1 already expands under query k's sweeps there,
+  // and its odd subtree beside its own sweeps costs them more than it saves -- measured, one rank of 8 alone with a null
+  // transport: 2.59-2.64 -> 2.45-2.56 ms per query one at a time, 2.09-2.13 -> 2.38 in a list (profiles/r06_rank_critical_path.md);
+  // comm.cpp says which it is through sp_shard_split_hint_
+  const bool shard_planes = rows && db->packed && h->p.planes() > 1 && h->p.num_per() >= 1024 && g_shard_split_hint != 0 &&
+                            tunable("expand_split_shards", 1) != 0;
+  W.long_sweep_follows = db && !db->sparse && (sweep_is_pipelined(h->p, *db) || shard_planes);
+  debug_stage(1);
+  if (tunable("query_cache_sync", 0) != 0) launch_cache_sync(nullptr, W.stream);  // diagnostic: L2 write-back + invalidate per query
+  run_begin(W, *pp, query, query_len, rows ? db->j0 : 0, rows ? db->nj : 0, plan);
+  W.long_sweep_follows = false;
+  HIP_CHECK(hipEventRecord(W.ev[1], W.stream));
+  q->state = 1;
+  q->for_sparse = db && db->sparse ? db : nullptr;
+  q->rows_j0 = rows ? db->j0 : 0;
+  q->rows_nj = rows ? db->nj : 0;
+}
+sp_query_t* spiral::query_open_sparse(const sp_params_t* h, const sp_pp_t* pp, const sp_db_t* db,
+                                      std::shared_ptr<const sp_db::SparseIndex> snapshot) {
+  return guarded_handle([&] {
+    need(db && db->sparse && snapshot, "null argument");
+    auto q = open_query(h, pp, db, std::move(snapshot));
+    q->ws->ensure_sweep();
+    return q;
+  });
+}
+void spiral::query_begin_opened(sp_query_t* q, const uint8_t* query, size_t query_len, const sp_db_t* db) {
+  need(q && query && q->state == 0, "null argument");
+  begin_opened(q, query, query_len, db);
 }
 
 // a begun query goes over `db` only if it was expanded for every row, or for the rows of exactly this row shard
@@ -292,7 +349,6 @@ int sp_debug_set(const char* name, long value) {
   return SP_OK;
 }
 // internal hooks for comm.cpp (not declared in the public header)
-static thread_local int g_shard_split_hint = 1;   // 0 while a list of sharded queries is being enqueued
 extern "C" void sp_shard_split_hint_(int on) { g_shard_split_hint = on; }
 // group = 0 of sp_process_queries_sharded_batched: 8 where a group of 8 takes the scatter-form pass on this shard and the shard
 // count is one where the batched list measured faster than the pipelined one (switch batch_scatter_max_g; profiles/sharded_batch_pass.md),
@@ -317,7 +373,7 @@ const char* sp_path_name(int bit) {
                                 "rccl_in_library", "fold_wave", "cu_split_overlap", "expand_split", "pipe_class_split",
                                 "sweep_batch_mfma", "custom_transport", "from_sweep_wave",
                                 "fold_tail_batched", "sweep_ring", "sweep_batch_mfma_two_tiles", "fold_wave8", "sweep_batch_planar",
-                                "expand_group", "expand_wave", "sweep_batch_scatter"};
+                                "expand_group", "expand_wave", "sweep_batch_scatter", "sparse_group_pass"};
   return bit >= 0 && bit < (int)(sizeof(names) / sizeof(names[0])) ? names[bit] : nullptr;
 }
 
@@ -751,29 +807,7 @@ sp_query_t* sp_query_begin_for_db(const sp_params_t* h, const sp_pp_t* pp, const
   return guarded_handle([&] {
     need(h && pp && query, "null argument");
     auto q = open_query(h, pp, db);
-    Workspace& W = *q->ws;
-    const bool rows = db && db->num_shards > 1 && db->col_G == 1;
-    const DeviceState::PrunedPlan* plan = q->sparse_index ? q->sparse_index->plan.get() : nullptr;
-    // a long (per-plane, pipelined) sweep follows: worth moving the fold's half of the expansion off the critical path
-    // (r06: also before the per-plane sweeps of a ROW SHARD -- the multi-GPU flows: the even subtree, pruned to the shard's rows,
-    // is short there, and the odd subtree + GSW side, which only the fold needs, then runs beside the sweeps and their exchanges
-    // instead of in front of them; switch expand_split_shards)
-    // NOT for a LIST of sharded queries (sp_process_queries_sharded): query k + 1 already expands under query k's sweeps there,
-    // and its odd subtree beside its own sweeps costs them more than it saves -- measured, one rank of 8 alone with a null
-    // transport: 2.59-2.64 -> 2.45-2.56 ms per query one at a time, 2.09-2.13 -> 2.38 in a list (profiles/r06_rank_critical_path.md);
-    // comm.cpp says which it is through sp_shard_split_hint_
-    const bool shard_planes = rows && db->packed && h->p.planes() > 1 && h->p.num_per() >= 1024 && g_shard_split_hint != 0 &&
-                              tunable("expand_split_shards", 1) != 0;
-    W.long_sweep_follows = db && !db->sparse && (sweep_is_pipelined(h->p, *db) || shard_planes);
-    debug_stage(1);
-    if (tunable("query_cache_sync", 0) != 0) launch_cache_sync(nullptr, W.stream);  // diagnostic: L2 write-back + invalidate per query
-    run_begin(W, *pp, query, query_len, rows ? db->j0 : 0, rows ? db->nj : 0, plan);
-    W.long_sweep_follows = false;
-    HIP_CHECK(hipEventRecord(W.ev[1], W.stream));
-    q->state = 1;
-    q->for_sparse = db && db->sparse ? db : nullptr;
-    q->rows_j0 = rows ? db->j0 : 0;
-    q->rows_nj = rows ? db->nj : 0;
+    begin_opened(q.get(), query, query_len, db);
     return q;
   });
 }

@@ -1,4 +1,4 @@
-// sp_process_query_batch: the two flows that answer a list of queries on one unsharded database.
+// sp_process_query_batch: the three flows that answer a list of queries on one unsharded database.
 #include <chrono>
 #include <deque>
 
@@ -76,29 +76,69 @@ int answer_in_flight(const BatchArgs& a) {
   return rc;
 }
 
+// What the two group flows below share: the queries in flight, oldest first (at most two groups: bounds the workspaces held), the
+// responses copied out so far, and the previous group's pass, which the next pass waits for.
+struct GroupsInFlight {
+  const BatchArgs& a;
+  const Params& p;
+  std::vector<sp_query_t*> all_qs;
+  size_t drained = 0;                // responses copied out so far
+  hipEvent_t prev_pass = nullptr;
+  size_t prev_group = 0;
+
+  explicit GroupsInFlight(const BatchArgs& args) : a(args), p(args.h->p) {}
+  ~GroupsInFlight() {
+    for (auto* q : all_qs) sp_query_free(q);
+  }
+
+  void drain(size_t count) {   // oldest `count` queries: wait, copy the response out, give the workspace back
+    for (size_t i = 0; i < count; i++) {
+      Workspace& W = *all_qs[i]->ws;
+      HIP_CHECK(hipStreamSynchronize(W.stream));
+      memcpy(a.out + (drained + i) * a.out_stride, W.h_response, p.response_bytes());
+      *a.out_len = p.response_bytes();
+      // (run_finish joins the second stream into the main one before the response copy, and a split-off odd expansion subtree
+      // -- not used by grouped expansions -- is joined before the fold: both streams are idle now)
+      all_qs[i]->streams_idle = !W.right_pending;
+    }
+    for (size_t i = 0; i < count; i++) sp_query_free(all_qs[i]);
+    all_qs.erase(all_qs.begin(), all_qs.begin() + count);
+    drained += count;
+  }
+  void keep_previous_group() {   // before a new group is enqueued: only the previous one stays in flight
+    if (all_qs.size() > prev_group) drain(all_qs.size() - prev_group);
+  }
+
+  void abandon() {  // let whatever was queued drain before the workspaces go back to the pool
+    for (auto* q : all_qs) (void)hipStreamSynchronize(q->ws->stream);
+    for (auto* q : all_qs) sp_query_free(q);
+    all_qs.clear();
+    prev_group = 0;
+    prev_pass = nullptr;
+  }
+  // an error other than out of memory: the first error text is kept, whatever is still in flight is drained and dropped
+  int fail(int rc) {
+    const std::string first_error = sp_last_error();
+    abandon();
+    sp_set_last_error_(first_error.c_str());
+    return rc;
+  }
+};
+
 // PACKED databases.  Groups of up to 8 queries -- 16 where the two-tile matrix-core pass applies (batch_group = 0, the default, asks
 // the kernel side; a positive value caps the group) -- share one database pass.  Nothing waits for a group's folds before the next
 // group's expansions and pass are queued (the passes themselves run one after the other: both are HBM-bound), and at
 // most two groups hold workspaces at a time.  Measured at C2 (profiles/r02_fold_batch_experiments.md): the overlap
 // buys nothing yet -- 16 queries take 2 x the time of 8, and 8 as 2 x 4 are slower (195 vs 236 queries/s) -- because
 // the batched sweep's workgroups fill every CU's register file, so a fold wave only starts when the pass drains.
-struct GroupedFlow {
-  const BatchArgs& a;
-  const Params& p;
+struct GroupedFlow : GroupsInFlight {
   // diagnostic (switch batch_trace): host time stamps of this call's phases on stderr, microseconds from entry
   const bool trace = tunable("batch_trace", 0) != 0;
-  std::vector<sp_query_t*> all_qs;   // queries in flight (at most two groups: bounds the workspaces held)
-  size_t drained = 0;                // responses copied out so far
-  hipEvent_t prev_pass = nullptr;
-  size_t prev_group = 0;
   int start = 0;   // first query not yet answered (a retry after an out-of-memory resumes here)
   bool use_planar = true, one_group = false;   // what the out-of-memory ladder gives up, in this order
   int group_max = 0;
 
-  explicit GroupedFlow(const BatchArgs& args) : a(args), p(args.h->p) {}
-  ~GroupedFlow() {
-    for (auto* q : all_qs) sp_query_free(q);
-  }
+  explicit GroupedFlow(const BatchArgs& args) : GroupsInFlight(args) {}
 
   void stamp(const char* what) const {
     if (trace)
@@ -120,21 +160,6 @@ struct GroupedFlow {
         group_max = SWEEP_BATCH_MAX;
       (void)hipGetLastError();
     }
-  }
-
-  void drain(size_t count) {   // oldest `count` queries: wait, copy the response out, give the workspace back
-    for (size_t i = 0; i < count; i++) {
-      Workspace& W = *all_qs[i]->ws;
-      HIP_CHECK(hipStreamSynchronize(W.stream));
-      memcpy(a.out + (drained + i) * a.out_stride, W.h_response, p.response_bytes());
-      *a.out_len = p.response_bytes();
-      // (run_finish joins the second stream into the main one before the response copy, and a split-off odd expansion subtree
-      // -- not used by grouped expansions -- is joined before the fold: both streams are idle now)
-      all_qs[i]->streams_idle = !W.right_pending;
-    }
-    for (size_t i = 0; i < count; i++) sp_query_free(all_qs[i]);
-    all_qs.erase(all_qs.begin(), all_qs.begin() + count);
-    drained += count;
   }
 
   // 1. expand every query of the group [g0, g0 + B) on its own stream.  (r05: the sixteen expansions of a group are 8-10 of a step's
@@ -204,8 +229,8 @@ struct GroupedFlow {
       const int B = std::min(group_max, a.batch - g0);
       if (one_group) {
         if (!all_qs.empty()) drain(all_qs.size());                        // nothing in flight beside this group
-      } else if (all_qs.size() > prev_group) {
-        drain(all_qs.size() - prev_group);                                // keep only the previous group in flight
+      } else {
+        keep_previous_group();
       }
       sp_query_t* const* qs = expand_group(g0, B);
       pass(qs, B);
@@ -213,14 +238,6 @@ struct GroupedFlow {
     }
     drain(all_qs.size());
     stamp("drained");
-  }
-
-  void abandon() {  // let whatever was queued drain before the workspaces go back to the pool
-    for (auto* q : all_qs) (void)hipStreamSynchronize(q->ws->stream);
-    for (auto* q : all_qs) sp_query_free(q);
-    all_qs.clear();
-    prev_group = 0;
-    prev_pass = nullptr;
   }
 
   // Steps 1 and 2 of the out-of-memory ladder: false when the step has nothing to give up.  (1) the digit-planar copy of the
@@ -266,12 +283,7 @@ struct GroupedFlow {
       else if (give_up(step))
         rc = guarded([&] { run_groups(); });
     }
-    if (rc != SP_OK) {  // keep the first error
-      const std::string first_error = sp_last_error();
-      abandon();
-      sp_set_last_error_(first_error.c_str());
-    }
-    return rc;
+    return rc != SP_OK ? fail(rc) : rc;
   }
 };
 
@@ -283,6 +295,98 @@ int answer_in_groups(const BatchArgs& a) {
   // the questions of the flow (LDS opt-in limit, free memory) are put to the CURRENT device: it has to be the database's
   const int rc = guarded([&] { check_device(a.db->device); });
   return rc != SP_OK ? rc : GroupedFlow(a).run();
+}
+
+
+// Sparse buckets (lib/server's SparseDb: the /private-read caller).  The list is cut into groups of at most SPARSE_GROUP_MAX = 8;
+// a group of at least `sparse_batch_min` members (switch; 0 = never, negative = the shipped default, at least 2 otherwise) shares ONE pass over the bucket
+// (k_sweep_sparse_batch: every item word read once per group), the rest of the list -- a last group below the threshold, a trailing
+// single query -- keeps the per-query flow above with its `batch_in_flight` depth.  A group takes one snapshot of the bucket's index,
+// held by all its members; each member is begun as sp_query_begin_for_db begins it (pruned expansion against that snapshot's plan
+// on its own stream), the pass runs on the first member's stream after every member's expansion and after the previous group's
+// pass, and the folds (all-zero shortcuts) run on the members' own streams.  As in GroupedFlow at most two groups hold workspaces,
+// every workspace's buffers exist before anything of its group is enqueued, and responses are copied out in list order.  Out of
+// memory: what is in flight is drained and dropped, the rest of the list is answered one query at a time.
+struct SparseGroupFlow : GroupsInFlight {
+  explicit SparseGroupFlow(const BatchArgs& args) : GroupsInFlight(args) {}
+
+  void group(int g0, int B) {
+    const size_t first = all_qs.size();
+    auto snapshot = const_cast<sp_db_t*>(a.db)->ensure_sparse_index();
+    for (int i = 0; i < B; i++) {   // every workspace (and its first-dimension output) before anything is enqueued
+      sp_query_t* q = query_open_sparse(a.h, a.pps[g0 + i], a.db, snapshot);
+      if (!q) {
+        if (null_handle_rc() == SP_E_OOM) throw OomError(sp_last_error());
+        throw ArgError(sp_last_error());
+      }
+      all_qs.push_back(q);
+    }
+    sp_query_t* const* qs = all_qs.data() + first;
+    for (int i = 0; i < B; i++) {
+      need(a.queries[g0 + i] != nullptr, "null argument");
+      query_begin_opened(qs[i], a.queries[g0 + i], a.query_lens[g0 + i], a.db);
+    }
+    debug_stage(2);
+    Workspace& W0 = group_pass_stream(qs, B);
+    if (prev_pass) HIP_CHECK(hipStreamWaitEvent(W0.stream, prev_pass, 0));
+    sparse_group_pass(*a.db, qs, B, W0.stream);
+    group_pass_done(qs, 0);
+    prev_pass = W0.ev[2];
+    debug_stage(3);
+    for (int i = 0; i < B; i++) {
+      if (i > 0) group_pass_done(qs, i);
+      qs[i]->ws->zero_shortcuts = true;   // lib/server's fold over a SparseDb (fold.rs:38-44)
+      qs[i]->state = 2;
+      run_finish(*qs[i]->ws, *qs[i]->pp, false);
+    }
+    prev_group = (size_t)B;
+  }
+
+  // the groups from `drained` on that reach the threshold; what is left of the list afterwards is the per-query flow's
+  void run_groups(int group_min) {
+    check_device(a.db->device);
+    for (int g0 = (int)drained; a.batch - g0 >= group_min; g0 += SPARSE_GROUP_MAX) {
+      keep_previous_group();
+      group(g0, std::min(SPARSE_GROUP_MAX, a.batch - g0));
+    }
+    drain(all_qs.size());
+  }
+
+  int run(int group_min) {
+    int rc = guarded([&] { run_groups(group_min); });
+    if (rc == SP_E_OOM) {   // the rest of the list one query at a time, one workspace; responses already copied out stay
+      abandon();
+      (void)hipGetLastError();
+      rc = SP_OK;
+      for (; (int)drained < a.batch && rc == SP_OK; drained++)
+        rc = sp_process_query(a.h, a.pps[drained], a.queries[drained], a.query_lens[drained], a.db, a.out + drained * a.out_stride,
+                              a.out_stride, a.out_len);
+      return rc;
+    }
+    if (rc != SP_OK) return fail(rc);
+    if ((int)drained == a.batch) return SP_OK;
+    BatchArgs rest = a;   // a last group below the threshold: up to `batch_in_flight` queries in flight
+    rest.pps += drained;
+    rest.queries += drained;
+    rest.query_lens += drained;
+    rest.batch -= (int)drained;
+    rest.out += drained * a.out_stride;
+    return answer_in_flight(rest);
+  }
+};
+
+int answer_sparse(const BatchArgs& a) {
+  long m = tunable("sparse_batch_min", SPARSE_BATCH_MIN_DEFAULT);
+  if (m < 0) m = SPARSE_BATCH_MIN_DEFAULT;   // (a negative value: the shipped default again, for a caller that had overridden it)
+  const int group_min = (int)std::max(2L, m);
+  if (m <= 0 || group_min > SPARSE_GROUP_MAX || a.batch < group_min || a.db->num_shards != 1 || a.db->col_G != 1)
+    return answer_in_flight(a);
+  if (a.out_stride < a.h->p.response_bytes()) {
+    sp_set_last_error_("out_stride smaller than response_bytes");
+    return SP_E_ARG;
+  }
+  const int rc = guarded([&] { check_device(a.db->device); });
+  return rc != SP_OK ? rc : SparseGroupFlow(a).run(group_min);
 }
 
 }  // namespace
@@ -297,5 +401,6 @@ extern "C" int sp_process_query_batch(const sp_params_t* h, const sp_pp_t* const
   tunables_new_call();  // the switches below are read before the first guarded() section of this call
   const BatchArgs a{h, pps, queries, query_lens, batch, db, out, out_stride, out_len, std::chrono::steady_clock::now()};
   const bool batched = db->packed && db->num_shards == 1 && db->col_G == 1 && !tunable("no_batch_sweep", 0);
+  if (db->sparse) return answer_sparse(a);
   return batched ? answer_in_groups(a) : answer_in_flight(a);
 }

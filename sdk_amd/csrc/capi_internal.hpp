@@ -133,6 +133,11 @@ float timed_reps(hipStream_t s, int iters, F&& once, float launches_per_rep = 1.
 // a query object with its workspace, nothing enqueued yet but the "begin" event (the group flow of sp_process_query_batch, which
 // expands its queries together: run_begin_group); state 0 until the caller has begun it
 sp_query_t* query_open(const sp_params_t* h, const sp_pp_t* pp);
+// the same for a member of a sparse bucket's group: it holds `snapshot` of the bucket's index, the group's one, instead of taking its
+// own, and its first-dimension output exists before anything is enqueued; query_begin_opened then begins it exactly as
+// sp_query_begin_for_db begins a query (pruned expansion against the snapshot's plan on the query's own stream; throws)
+sp_query_t* query_open_sparse(const sp_params_t* h, const sp_pp_t* pp, const sp_db_t* db, std::shared_ptr<const sp_db::SparseIndex> snapshot);
+void query_begin_opened(sp_query_t* q, const uint8_t* query, size_t query_len, const sp_db_t* db);
 void finish_impl(sp_query_t* q, bool premod, uint8_t* out, size_t out_cap, size_t* out_len);
 
 // what one workspace of a batched group may need, as the group planner and the planar copy estimate it
@@ -150,6 +155,10 @@ Workspace& group_pass_stream(sp_query_t* const* qs, int B);
 // ... and once the pass is enqueued, member i's ev[2] is recorded on its own stream, which for i > 0 first waits for the first
 // member's ev[2]: call for i = 0 first
 void group_pass_done(sp_query_t* const* qs, int i);
+
+// One pass over the sparse bucket `db` for the group qs[0 .. B), B <= SPARSE_GROUP_MAX, all begun on one snapshot of its index (the
+// first member's is read): enqueued on `s`; the order around it is the caller's (group_pass_stream / group_pass_done)
+void sparse_group_pass(const sp_db& db, sp_query_t* const* qs, int B, hipStream_t s);
 
 // sp_query_sweep_scatter_group's checks (nothing enqueued on an error) and its prepared descriptor: the group's pass in the
 // reduce-scatter layout on the first query's stream; false: this group or shape is not the matrix-core pass's -- the caller sweeps

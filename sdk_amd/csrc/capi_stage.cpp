@@ -95,6 +95,20 @@ int sp_bench_sweep_ex(sp_query_t* q, const sp_db_t* db, int iters, int per_plane
 
 int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, int iters, float* ms_per_pass) {
   return guarded([&] {
+    if (qs && db && db->sparse) {   // a sparse bucket: the group's one pass (k_sweep_sparse_batch), 1 .. 8 queries begun for this bucket
+      need(ms_per_pass && iters > 0 && batch >= 1 && batch <= SPARSE_GROUP_MAX, "bad argument");
+      check_device(db->device);
+      for (int i = 0; i < batch; i++) {
+        need(qs[i] && qs[i]->state >= 1, "query not begun");
+        need(qs[i]->params == db->params, "query and db were created for different params");
+        qs[i]->ws->ensure_sweep();
+        HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream));   // expansions done: the pass is timed alone
+        HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream2));
+      }
+      hipStream_t s = qs[0]->ws->stream;
+      *ms_per_pass = timed_reps(s, iters, [&] { sparse_group_pass(*db, qs, batch, s); });
+      return;
+    }
     need(qs && db && ms_per_pass && iters > 0 && batch >= 1 && batch <= sweep_batch_group_max(db ? db->np_local : 0, db ? db->nj : 0), "bad argument");
     need(db->packed && db->num_shards == 1 && db->col_G == 1, "the batched pass needs an unsharded PACKED database");
     check_device(db->device);

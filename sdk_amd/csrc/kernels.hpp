@@ -79,7 +79,8 @@ enum PathBit : u64 {
   PATH_SWEEP_PLANAR = 1ull << 31,     // k_sweep_planar: the 9 .. 16-query pass over the digit-planar copy of the database
   PATH_EXPAND_GROUP = 1ull << 32,     // a group's expansions with every round's launches shared (grid dimension = query; r06)
   PATH_EXPAND_WAVE = 1ull << 33,      // k_expand_wave: a round's many-digit side on the wave-per-transform NTT (r06)
-  PATH_SWEEP_BATCH_SCATTER = 1ull << 34 // k_sweep_mfma_scatter: the one-tile batched pass over a row shard, reduce-scatter layout
+  PATH_SWEEP_BATCH_SCATTER = 1ull << 34,// k_sweep_mfma_scatter: the one-tile batched pass over a row shard, reduce-scatter layout
+  PATH_SWEEP_SPARSE_GROUP = 1ull << 35  // k_sweep_sparse_batch: one pass over a sparse bucket for a group of up to 8 queries
 };
 // Run-time tunables (sp_debug_set / environment SPIRAL_<NAME>): read on every launch, so that variants can be A/B
 // measured inside one process on ONE database allocation (HBM placement alone moves the sweep by +-5 %).
@@ -488,6 +489,19 @@ void launch_sparse_item_encode(const DevTables& T, const uint8_t* bytes, int ite
 // ct index first + step * j; out = sweep-native [plane][r][crt][z][ii]
 void launch_sweep_sparse(const DevTables& T, const int* col_ptr, const int* col_rows, const int* col_slots, const u64* polys,
                          int planes, const u32* v, int first, int step, u32* out, int num_per, hipStream_t s);
+// ... and for a group of 1 .. SPARSE_GROUP_MAX queries in ONE pass over the bucket: every item word is read once per group.
+// Member b reads its own expanded ciphertexts v[b] and writes its own out[b] (layouts as above); first / step are shared.
+constexpr int SPARSE_GROUP_MAX = 8;
+// switch sparse_batch_min: the smallest group of a list on a sparse bucket that shares one pass (0 = never: every query sweeps alone;
+// negative = this default).  Measured at nu = (9, 7), 16 % and 100 % full (profiles/sparse_batch_pass.md): groups of 2, 3, 4, 5 and 8
+// and lists of 64 all beat the per-query flow on both buckets by more than the spread
+constexpr long SPARSE_BATCH_MIN_DEFAULT = 2;
+struct SparseGroup {
+  const u32* v[SPARSE_GROUP_MAX];
+  u32* out[SPARSE_GROUP_MAX];
+};
+void launch_sweep_sparse_batch(const DevTables& T, const int* col_ptr, const int* col_rows, const int* col_slots, const u64* polys,
+                               int planes, const SparseGroup& members, int nq, int first, int step, int num_per, hipStream_t s);
 
 // sweep-native out [plane][r][crt][z][ii] -> reference out[ii].data[r*2N + crt*N + z] (u64) for one plane
 void launch_sweep_out_to_ref(u64* out, const u32* in, int num_per, hipStream_t s);

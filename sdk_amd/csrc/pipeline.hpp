@@ -82,6 +82,9 @@ void run_begin_group(Workspace* const* Ws, const sp_pp* const* pps, const uint8_
 void run_begin(Workspace& W, const sp_pp& pp, const uint8_t* query, size_t query_len, int j0 = 0, int nj = 0,
                const DeviceState::PrunedPlan* plan = nullptr);
 void run_sweep_sparse(Workspace& W, const sp_db& db, const int* col_ptr, const int* col_rows, const int* col_slots);
+// ... for the workspaces of a group of up to SPARSE_GROUP_MAX queries in one pass (every item word read once), enqueued on `s`
+void run_sweep_sparse_group(Workspace* const* Ws, int B, const sp_db& db, const int* col_ptr, const int* col_rows, const int* col_slots,
+                            hipStream_t s);
 // expansion schedule pruned to an arbitrary set of first-dimension rows (rows[j] != 0), lists uploaded
 std::unique_ptr<DeviceState::PrunedPlan> build_pruned_plan_rows(const Params& P, const std::vector<char>& rows);
 void run_sweep(Workspace& W, const sp_db& db);

@@ -1263,6 +1263,21 @@ void run_sweep_sparse(Workspace& W, const sp_db& db, const int* col_ptr, const i
                       p.db_dim_2 > 0 ? 2 : 1, W.sweep_out.p, (int)p.num_per(), W.stream);
 }
 
+// the same product for a group of queries (one Params: one `step`) in one pass over the bucket: member b reads its own expanded
+// ciphertexts and writes its own first-dimension output
+void run_sweep_sparse_group(Workspace* const* Ws, int B, const sp_db& db, const int* col_ptr, const int* col_rows, const int* col_slots,
+                            hipStream_t s) {
+  const Params& p = *Ws[0]->P;
+  SparseGroup g{};
+  for (int b = 0; b < B; b++) {
+    Ws[b]->ensure_sweep();
+    g.v[b] = Ws[b]->v.p;
+    g.out[b] = Ws[b]->sweep_out.p;
+  }
+  launch_sweep_sparse_batch(Ws[0]->D->T, col_ptr, col_rows, col_slots, db.polys.p, (int)p.planes(), g, B, 0, p.db_dim_2 > 0 ? 2 : 1,
+                            (int)p.num_per(), s);
+}
+
 // The query flows' fold: the workspace's threshold (read when it was created: the digit staging of the unfused levels is sized
 // from it), lowered -- never raised -- by the run-time switch fused_min_pairs_cap (in-process A/B); delta-form tail.  below_q only
 // for ciphertexts this library has just produced itself (from_ntt / fold outputs): everything else (ciphertexts gathered from

@@ -115,4 +115,108 @@ void launch_sweep_sparse(const DevTables& T, const int* col_ptr, const int* col_
   launched(PATH_SWEEP_SPARSE, "k_sweep_sparse");
 }
 
+// ---- the same multiply for a GROUP of queries that share one pass over the bucket -------------------------------------
+// grid (num_per, planes, N / (256 ZT)): thread tau of z-slab s owns the ZT consecutive z from (256 s + tau) ZT, so the B x 4 x ZT
+// u64 sums stay in vector registers (B = 8 and 4: ZT = 2, 128 / 64 VGPRs of sums; B = 2: ZT = 4, 64.  B = 4 with ZT = 4 was measured
+// and is a third slower per pass: profiles/sparse_batch_pass.md).  Every item word is loaded ONCE per group
+// (16-byte non-temporal loads: nothing reads it again before the next pass) and multiplied into every query's four (r, crt) sums;
+// the query rows (plain loads: every column re-reads them) are the members' own expanded ciphertexts v_b[ct][r][crt][z] and the
+// sums go to the members' own out_b[plane][r][crt][z][ii].  `first` / `step` are the group's: its members share Params.
+// A group of nq < B members runs the B body with DEAD slots: they read member 0's rows and store nothing.
+// Exact sums as in k_sweep_sparse: products < 2^56, a Barrett fold after every 255 items of a column (a folded sum is < q < 2^28:
+// 255 * 2^56 + 2^28 < 2^64), so the sums are canonical after the loop; absent columns write zeros.
+typedef u64 sp_u64x2_t __attribute__((ext_vector_type(2)));
+typedef u32 sp_u32x2_t __attribute__((ext_vector_type(2)));
+typedef u32 sp_u32x4_t __attribute__((ext_vector_type(4)));
+template <int B>
+__global__ __launch_bounds__(256) void k_sweep_sparse_batch(DevTables T, const int* col_ptr, const int* col_rows, const int* col_slots,
+                                                            const u64* polys, int planes, SparseGroup g, int nq, int first, int step,
+                                                            int num_per) {
+  constexpr int ZT = B == 2 ? 4 : 2;
+  const int ii = blockIdx.x, plane = blockIdx.y;
+  const int z0 = ((int)blockIdx.z * 256 + (int)threadIdx.x) * ZT;
+  const ModConst m0 = T.c.mod[0], m1 = T.c.mod[1];
+  u64 a[B][4][ZT];
+#pragma unroll
+  for (int b = 0; b < B; b++)
+#pragma unroll
+    for (int rc = 0; rc < 4; rc++)
+#pragma unroll
+      for (int k = 0; k < ZT; k++) a[b][rc][k] = 0;
+  const int e1 = col_ptr[ii + 1];
+  for (int e = col_ptr[ii]; e < e1;) {
+    const int stop = e1 - e > 255 ? e + 255 : e1;
+    for (; e < stop; e++) {
+      const u64* ip = polys + ((size_t)col_slots[e] * planes + plane) * N + z0;
+      const size_t qo = (size_t)(first + step * col_rows[e]) * 4 * N + z0;  // [r][crt][z]
+      u32 bl[ZT], bh[ZT];
+#pragma unroll
+      for (int k = 0; k < ZT; k += 2) {
+        const sp_u64x2_t w = __builtin_nontemporal_load(reinterpret_cast<const sp_u64x2_t*>(ip + k));
+        bl[k] = (u32)w.x; bh[k] = (u32)(w.x >> 32);
+        bl[k + 1] = (u32)w.y; bh[k + 1] = (u32)(w.y >> 32);
+      }
+#pragma unroll
+      for (int b = 0; b < B; b++) {
+        const u32* q = g.v[b] + qo;
+#pragma unroll
+        for (int rc = 0; rc < 4; rc++) {   // r0 crt0, r0 crt1, r1 crt0, r1 crt1
+          u32 x[ZT];
+          if constexpr (ZT == 4) {
+            const sp_u32x4_t t = *reinterpret_cast<const sp_u32x4_t*>(q + rc * N);
+            x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
+          } else {
+            const sp_u32x2_t t = *reinterpret_cast<const sp_u32x2_t*>(q + rc * N);
+            x[0] = t.x; x[1] = t.y;
+          }
+#pragma unroll
+          for (int k = 0; k < ZT; k++) a[b][rc][k] += (u64)x[k] * ((rc & 1) ? bh[k] : bl[k]);
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < B; b++)
+#pragma unroll
+      for (int rc = 0; rc < 4; rc++)
+#pragma unroll
+        for (int k = 0; k < ZT; k++) a[b][rc][k] = reduce64(a[b][rc][k], (rc & 1) ? m1 : m0);
+  }
+  // out_b[plane][r][crt][z][ii]
+  const size_t rc_words = (size_t)N * num_per;
+  const size_t o0 = (size_t)plane * 4 * rc_words + (size_t)z0 * num_per + ii;
+#pragma unroll
+  for (int b = 0; b < B; b++) {
+    if (b >= nq) break;
+    u32* o = g.out[b] + o0;
+#pragma unroll
+    for (int rc = 0; rc < 4; rc++)
+#pragma unroll
+      for (int k = 0; k < ZT; k++) o[rc * rc_words + (size_t)k * num_per] = (u32)a[b][rc][k];
+  }
+}
+template <int B>
+static void launch_sweep_sparse_batch_b(const DevTables& T, const int* col_ptr, const int* col_rows, const int* col_slots,
+                                        const u64* polys, int planes, const SparseGroup& g, int nq, int first, int step, int num_per,
+                                        hipStream_t s) {
+  constexpr int ZT = B == 2 ? 4 : 2;
+  hipLaunchKernelGGL(k_sweep_sparse_batch<B>, dim3(num_per, planes, N / (256 * ZT)), dim3(256), 0, s, T, col_ptr, col_rows, col_slots,
+                     polys, planes, g, nq, first, step, num_per);
+}
+// 1 <= nq <= SPARSE_GROUP_MAX is the caller's to check (sparse_group_pass, capi.cpp)
+void launch_sweep_sparse_batch(const DevTables& T, const int* col_ptr, const int* col_rows, const int* col_slots, const u64* polys,
+                               int planes, const SparseGroup& members, int nq, int first, int step, int num_per, hipStream_t s) {
+  SparseGroup g = members;
+  for (int b = nq; b < SPARSE_GROUP_MAX; b++) {   // dead slots: valid rows to read, never stored
+    g.v[b] = g.v[0];
+    g.out[b] = nullptr;
+  }
+  if (nq <= 2)
+    launch_sweep_sparse_batch_b<2>(T, col_ptr, col_rows, col_slots, polys, planes, g, nq, first, step, num_per, s);
+  else if (nq <= 4)
+    launch_sweep_sparse_batch_b<4>(T, col_ptr, col_rows, col_slots, polys, planes, g, nq, first, step, num_per, s);
+  else
+    launch_sweep_sparse_batch_b<8>(T, col_ptr, col_rows, col_slots, polys, planes, g, nq, first, step, num_per, s);
+  launched(PATH_SWEEP_SPARSE | PATH_SWEEP_SPARSE_GROUP, "k_sweep_sparse_batch");
+}
+
 }  // namespace spiral
