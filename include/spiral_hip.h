@@ -128,6 +128,25 @@ int sp_db_load_items(sp_db_t*, const uint8_t* file, size_t file_len);
  * reference's SparseDb yields for absent rows).  `data` is zero-padded to db_item_size.  On a row shard
  * that does not hold the item's row the call is a no-op. */
 int sp_db_update_item(sp_db_t*, size_t item_idx, const uint8_t* data, size_t len);
+/* Upsert n items in one call: what n calls of sp_db_update_item(item_idx[i], data[i], lens[i]), i = 0 .. n-1 in that order, leave
+ * on the handle -- a later entry for an index wins (the list is deduplicated on the host, last occurrence kept, before anything is
+ * launched), a sparse bucket's new keys take their slots in order of first appearance and its store grows once, entries a row or
+ * column shard does not hold are skipped.  The bytes travel through the handle's upload buffer in windows of at most
+ * db_load_window bytes; per window one copy, one encode launch over all its items ((item, plane) workgroups on a sparse bucket,
+ * (touched quad, plane) workgroups on a dense database), one patch launch when a digit-planar copy stands, one device
+ * synchronisation.  Every index and length is checked before anything is written: SP_E_ARG leaves the handle as it was. */
+int sp_db_update_items(sp_db_t*, const size_t* item_idx, const uint8_t* const* data, const size_t* lens, size_t n);
+/* The body of POST /update-row (lib/server/src/bin/server.rs:31-43 -> update_many_items, db/loading.rs:361-377): records
+ * be32 chunk_len | be32 item index | chunk_len - 4 item bytes, applied through sp_db_update_items.  *largest_update = the largest
+ * chunk_len (the 4 index bytes included), what the reference returns (loading.rs:368-370).  Lengths: a record carries
+ * 0 .. db_item_size item bytes, as sp_db_update_item; the reference's bound (update_item, loading.rs:305-310) is
+ * instances * n * n * bytes_per_chunk, which is db_item_size rounded up to whole chunks: the two differ only where db_item_size
+ * is not a multiple of the chunk count, and there the reference's extra bytes lie past the item.  A faulty record -- cut inside
+ * its length or payload, chunk_len < 4, too long, index >= num_items -- ends the call with SP_E_ARG and a text that names the
+ * record number and its byte offset; the records before it HAVE been applied and *applied is their count (the reference applies
+ * while it parses and then returns Err or panics: the applied prefix is what its clients see too).  An empty body is SP_OK with
+ * *applied = 0.  Records a shard skips count as applied.  applied / largest_update may be null. */
+int sp_db_update_rows(sp_db_t*, const uint8_t* body, size_t body_len, size_t* applied, size_t* largest_update);
 /* Synthetic benchmark database generated on the device: reference-layout word index i holds
  * sp_synth_word(seed, i).  (Roofline runs at sizes no host buffer can hold.) */
 int sp_db_fill_synthetic(sp_db_t*, uint64_t seed);
@@ -311,7 +330,8 @@ int sp_comm_describe(const sp_comm_t*, char* buf, size_t cap);
 /* ------------------------------------------------------ request layer (lib/server's binary without the HTTP transport)
  * ServerState of lib/server/src/bin/server.rs:21-28: the params, the resident database and the
  * RwLock<HashMap<uuid, PublicParameters>> that POST /setup fills and POST /private-read consults.  `params` and `db` are
- * borrowed and must outlive the handle.  All entry points may be called concurrently from several host threads. */
+ * borrowed and must outlive the handle.  All entry points may be called concurrently from several host threads; writes to the
+ * database while the server answers go through sp_server_update_row. */
 typedef struct sp_server sp_server_t;
 sp_server_t* sp_server_create(const sp_params_t* params, const sp_db_t* db);
 void sp_server_free(sp_server_t*);
@@ -335,6 +355,13 @@ int sp_server_private_read(sp_server_t*, const uint8_t* const* requests, const s
  * serde_json / the base64 crate produce: no spaces, standard alphabet, padding). */
 int sp_server_private_read_json(sp_server_t*, const char* body, size_t body_len, char* out, size_t out_cap, size_t* out_len);
 size_t sp_server_private_read_json_bound(const sp_server_t*, int n_queries); /* out_cap that always suffices */
+/* POST /update-row (bin/server.rs:31-43) on the raw body: sp_db_update_rows on the server's database under the write side of the
+ * server's reader-writer lock for it (RwLock<SparseDb>, bin/server.rs:24,35); sp_server_private_read[_json] hold the read side
+ * (:102) for their whole list, so a list is answered from the bucket before or after a body, never from the middle of one.  `db`
+ * must be the handle the server was created on (sp_server_create took it const): any other is SP_E_ARG.  out = the reference's
+ * reply {"status":"done updating", "loading_time_us":N, "largest_update":M} (NUL-terminated; 128 bytes always suffice).  A faulty
+ * record: sp_db_update_rows' status and text, the prefix applied, nothing written to out. */
+int sp_server_update_row(sp_server_t*, sp_db_t* db, const uint8_t* body, size_t body_len, char* out, size_t out_cap, size_t* out_len);
 
 /* Stand-alone timed sweep for the roofline measurement: issues the db-sweep launches of one query over `db`
  * (the same kernel and launch shapes sp_process_query uses) `iters` times with the query slice of `q`, HIP events

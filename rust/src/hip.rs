@@ -81,6 +81,8 @@ pub mod sys {
         pub fn sp_db_load(db: *mut sp_db_t, words: *const u64, n_words: usize) -> c_int;
         pub fn sp_db_load_items(db: *mut sp_db_t, file: *const u8, file_len: usize) -> c_int;
         pub fn sp_db_update_item(db: *mut sp_db_t, item_idx: usize, data: *const u8, len: usize) -> c_int;
+        pub fn sp_db_update_items(db: *mut sp_db_t, item_idx: *const usize, data: *const *const u8, lens: *const usize, n: usize) -> c_int;
+        pub fn sp_db_update_rows(db: *mut sp_db_t, body: *const u8, body_len: usize, applied: *mut usize, largest_update: *mut usize) -> c_int;
         pub fn sp_db_fill_synthetic(db: *mut sp_db_t, seed: u64) -> c_int;
         pub fn sp_db_prepare_batch(db: *mut sp_db_t, built: *mut c_int) -> c_int;
         pub fn sp_db_batch_copy_bytes(db: *const sp_db_t) -> usize;
@@ -156,6 +158,8 @@ pub mod sys {
         pub fn sp_server_private_read_json(s: *mut sp_server_t, body: *const c_char, body_len: usize, out: *mut c_char,
                                            out_cap: usize, out_len: *mut usize) -> c_int;
         pub fn sp_server_private_read_json_bound(s: *const sp_server_t, n_queries: c_int) -> usize;
+        pub fn sp_server_update_row(s: *mut sp_server_t, db: *mut sp_db_t, body: *const u8, body_len: usize, out: *mut c_char,
+                                    out_cap: usize, out_len: *mut usize) -> c_int;
         // ---- measurement aids
         pub fn sp_sweep_launches(p: *const sp_params_t, db: *const sp_db_t) -> c_int;
         pub fn sp_bench_sweep(q: *mut sp_query_t, db: *const sp_db_t, iters: c_int, ms_per_launch: *mut f32) -> c_int;
@@ -337,6 +341,23 @@ impl Database {
     /// `/write`: lib/server/src/db/loading.rs:317-359 `update_item_raw`.
     pub fn update_item(&mut self, item_idx: usize, data: &[u8]) {
         must(check(unsafe { sys::sp_db_update_item(self.0, item_idx, data.as_ptr(), data.len()) }))
+    }
+    /// `items` upserted in one call (`sp_db_update_items`): what `update_item` on each pair in order leaves, a later pair for an
+    /// index winning.
+    pub fn update_items(&mut self, items: &[(usize, &[u8])]) {
+        let idx: Vec<usize> = items.iter().map(|p| p.0).collect();
+        let ptr: Vec<*const u8> = items.iter().map(|p| p.1.as_ptr()).collect();
+        let len: Vec<usize> = items.iter().map(|p| p.1.len()).collect();
+        must(check(unsafe { sys::sp_db_update_items(self.0, idx.as_ptr(), ptr.as_ptr(), len.as_ptr(), items.len()) }))
+    }
+    /// The body of `/update-row` (lib/server/src/db/loading.rs:361-377 `update_many_items`): `Ok(largest_update)`, or the error of
+    /// the first faulty record with the count of records applied before it.
+    pub fn update_rows(&mut self, body: &[u8]) -> Result<usize, (HipError, usize)> {
+        let (mut applied, mut largest) = (0usize, 0usize);
+        match check(unsafe { sys::sp_db_update_rows(self.0, body.as_ptr(), body.len(), &mut applied, &mut largest) }) {
+            Ok(()) => Ok(largest),
+            Err(e) => Err((e, applied)),
+        }
     }
     pub fn fill_synthetic(&mut self, seed: u64) {
         must(check(unsafe { sys::sp_db_fill_synthetic(self.0, seed) }))
@@ -565,6 +586,21 @@ impl<'a> Server<'a> {
         let mut out = vec![0u8; cap];
         let mut n = 0usize;
         check(unsafe { sys::sp_server_private_read_json(self.h, body.as_ptr() as *const c_char, body.len(), out.as_mut_ptr() as *mut c_char, out.len(), &mut n) })?;
+        out.truncate(n);
+        Ok(String::from_utf8(out).unwrap())
+    }
+    /// POST /update-row (bin/server.rs:31-43): the raw body in, the reference's reply string out.  Holds the write side of the
+    /// server's lock for its database; `private_read` holds the read side.
+    ///
+    /// # Safety
+    /// This writes the database the server borrows shared (`&'a Database`): only calls made through this `Server` wait for the
+    /// write to end.  While the call runs, no thread may use that `Database` directly (`process_query`, `Query::sweep`, ...): a
+    /// read outside the server's lock can see a body half applied.  Route every read through `private_read` while the server
+    /// takes updates.
+    pub unsafe fn update_row(&self, body: &[u8]) -> Result<String, HipError> {
+        let mut out = vec![0u8; 128];
+        let mut n = 0usize;
+        check(sys::sp_server_update_row(self.h, self._db.0, body.as_ptr(), body.len(), out.as_mut_ptr() as *mut c_char, out.len(), &mut n))?;
         out.truncate(n);
         Ok(String::from_utf8(out).unwrap())
     }

@@ -65,8 +65,7 @@ def main():
     wins = {n: True for n in LISTS}
     try:
         for pct, target in ((16, 10485), (100, 1 << 16)):
-            for idx in order[filled:target]:
-                gdb.update_item(int(idx), b"\x01\x02\x03")
+            gdb.update_items([(int(idx), b"\x01\x02\x03") for idx in order[filled:target]])   # one call (sp_db_update_items)
             filled = target
             for m in (0, 2):                                  # warm both flows: workspaces, code objects
                 set_min(m)

@@ -73,6 +73,201 @@ const uint8_t* upload_item(sp_db& d, const uint8_t* data, size_t len) {
   return d.upload.p;
 }
 
+
+// room for `slots` polynomial sets in a sparse bucket's store: amortised doubling from 64, contents preserved (caller holds mu)
+void sparse_reserve(sp_db& d, size_t slots) {
+  size_t cap = d.slots_cap;
+  while (cap < slots) cap = std::max<size_t>(64, cap * 2);
+  if (cap == d.slots_cap) return;
+  const size_t poly_words = d.params->p.planes() * POLY_LEN;
+  DevBuf<u64> bigger(cap * poly_words);
+  if (d.slots_cap) HIP_CHECK(hipMemcpy(bigger.p, d.polys.p, d.slots_cap * poly_words * 8, hipMemcpyDeviceToDevice));
+  if (d.slots_cap && tunable("h2d_cache_sync", 0) != 0) launch_cache_sync(nullptr, 0);  // (as h2d_sync)
+  d.polys = std::move(bigger);
+  d.slots_cap = cap;
+}
+
+// ---- sp_db_update_items: many upserts per launch
+struct UpsertRec {
+  size_t idx;
+  const uint8_t* data;
+  size_t len;
+};
+// One upload window of a bulk upsert: `groups` encode groups (a sparse bucket's items, a dense database's touched quads) from
+// `first`, whose records carry `bytes` bytes; `cells` = entries of the planar patch list.  The device image of a window is
+// [group table | cell table | item bytes], each part from a 16-byte boundary: one copy per window.
+struct UpsertWindow {
+  size_t first = 0, groups = 0, bytes = 0, cells = 0;
+};
+size_t round16(size_t x) { return (x + 15) & ~(size_t)15; }
+// the windows of a call: at most db_load_window item bytes each (a group larger than that travels alone) and at most
+// UPSERT_MAX_GROUP_PLANES / planes groups, which keeps the encode launches and the patch launch below 2^31 blocks along grid.x
+template <typename BytesOf>
+std::vector<UpsertWindow> upsert_windows(size_t n_groups, size_t planes, BytesOf&& bytes_of) {
+  const size_t max_win = (size_t)std::max<long>(1, tunable("db_load_window", (long)512 << 20));
+  const size_t max_groups = std::max<size_t>(1, UPSERT_MAX_GROUP_PLANES / planes);
+  std::vector<UpsertWindow> wins;
+  for (size_t g = 0; g < n_groups; g++) {
+    const size_t b = bytes_of(g);
+    if (wins.empty() || wins.back().groups >= max_groups || (wins.back().groups && wins.back().bytes + b > max_win)) {
+      wins.emplace_back();
+      wins.back().first = g;
+    }
+    wins.back().groups++;
+    wins.back().bytes += b;
+  }
+  return wins;
+}
+
+// a sparse bucket: update_many_items (loading.rs:361-377) over sparse_db.rs:42-48 upsert; `recs` hold each index once, in order of
+// first appearance (caller holds mu)
+void upsert_sparse(sp_db& d, const std::vector<UpsertRec>& recs) {
+  sp_params* h = const_cast<sp_params*>(d.params);
+  const Params& p = h->p;
+  DeviceState& D = h->device_state();
+  const size_t planes = p.planes();
+  // new keys: slots in order of first appearance, the store grown once for all of them, before the first kernel
+  size_t n_new = 0;
+  for (const UpsertRec& r : recs) n_new += d.slot_of.count(r.idx) == 0;
+  sparse_reserve(d, d.slot_of.size() + n_new);
+  const std::vector<UpsertWindow> wins = upsert_windows(recs.size(), planes, [&](size_t g) { return recs[g].len; });
+  size_t image = 1;
+  for (const UpsertWindow& w : wins) image = std::max(image, round16(w.groups * sizeof(SparseItemRec)) + w.bytes);
+  d.upload.ensure(image);
+  std::vector<uint8_t> host(image);
+  if (n_new && !d.rows_dirty) {  // does a new item open a new first-dimension row?  (then the pruned expansion plan changes)
+    std::vector<char> row_set(p.dim0(), 0);
+    for (const auto& kv : d.slot_of) row_set[kv.first / p.num_per()] = 1;
+    for (const UpsertRec& r : recs)
+      if (!row_set[r.idx / p.num_per()]) d.rows_dirty = true;
+  }
+  std::vector<SparseItemRec> table;
+  for (const UpsertWindow& w : wins) {
+    table.resize(w.groups);
+    const size_t bytes0 = round16(w.groups * sizeof(SparseItemRec));
+    size_t off = 0;
+    for (size_t g = 0; g < w.groups; g++) {
+      const UpsertRec& r = recs[w.first + g];
+      auto it = d.slot_of.find(r.idx);
+      if (it == d.slot_of.end()) it = d.slot_of.emplace(r.idx, d.slot_of.size()).first;
+      table[g] = SparseItemRec{(unsigned long long)off, (int)r.len, (int)it->second};
+      if (r.len) memcpy(host.data() + bytes0 + off, r.data, r.len);
+      off += r.len;
+    }
+    memcpy(host.data(), table.data(), w.groups * sizeof(SparseItemRec));
+    h2d_sync(d.upload.p, host.data(), bytes0 + w.bytes);
+    launch_sparse_items_encode(D.T, d.upload.p + bytes0, reinterpret_cast<const SparseItemRec*>(d.upload.p), w.groups,
+                               (int)p.db_item_size, (int)chunk_bytes(p), (int)pt_bits(p), (u32)p.pt_modulus, d.polys.p, (int)planes, 0);
+    HIP_CHECK(hipDeviceSynchronize());
+  }
+  if (n_new) d.index_dirty = true;   // overwrites (the reference's upsert of an existing key) leave the index alone
+}
+
+// a dense database or shard: the records it holds grouped by quad (local row pair, local column pair), a quad listed once with every
+// item of it that the call updates -- two items of a quad share a PACKED lane group and must be one workgroup's (caller holds mu)
+void upsert_dense(sp_db& d, const std::vector<UpsertRec>& recs) {
+  sp_params* h = const_cast<sp_params*>(d.params);
+  const Params& p = h->p;
+  DeviceState& D = h->device_state();
+  const size_t planes = p.planes(), npq = ((size_t)d.np_local + 1) / 2;
+  struct Quad {
+    int jp, q;
+    long rec[4];
+  };
+  std::vector<Quad> quads;
+  std::unordered_map<size_t, size_t> quad_of;
+  for (size_t i = 0; i < recs.size(); i++) {
+    const size_t j = recs[i].idx / p.num_per(), ii = recs[i].idx % p.num_per();
+    if ((int)j < d.j0 || (int)j >= d.j0 + d.nj) continue;   // row lives on another shard
+    if ((int)(ii % (size_t)d.col_G) != d.col_g) continue;   // column lives on another shard
+    const int jl = (int)j - d.j0, il = (int)(ii / (size_t)d.col_G);
+    auto it = quad_of.emplace((size_t)(jl / 2) * npq + (size_t)(il / 2), quads.size());
+    if (it.second) quads.push_back(Quad{jl / 2, il / 2, {-1, -1, -1, -1}});
+    quads[it.first->second].rec[(jl & 1) * 2 + (il & 1)] = (long)i;
+  }
+  auto quad_bytes = [&](size_t g) {
+    size_t b = 0;
+    for (long r : quads[g].rec) b += r >= 0 ? recs[(size_t)r].len : 0;
+    return b;
+  };
+  std::vector<UpsertWindow> wins = upsert_windows(quads.size(), planes, quad_bytes);
+  const bool patch = d.planar_state == 1;   // a planar copy follows its items: the 16-row groups of the touched columns are regathered
+  size_t image = 1;
+  for (UpsertWindow& w : wins) {
+    w.cells = patch ? 2 * w.groups : 0;   // (a quad's two rows share a 16-row group: its two columns; an upper bound, see below)
+    image = std::max(image, round16(w.groups * sizeof(DbQuadRec)) + round16(w.cells * sizeof(PlanarPatchCell)) + w.bytes);
+  }
+  d.upload.ensure(image);
+  std::vector<uint8_t> host(image);
+  std::vector<DbQuadRec> table;
+  std::vector<PlanarPatchCell> cells;
+  std::unordered_map<size_t, char> cell_seen;
+  for (const UpsertWindow& w : wins) {
+    table.resize(w.groups);
+    cells.clear();
+    cell_seen.clear();
+    const size_t cells0 = round16(w.groups * sizeof(DbQuadRec)), bytes0 = cells0 + round16(w.cells * sizeof(PlanarPatchCell));
+    size_t off = 0;
+    for (size_t g = 0; g < w.groups; g++) {
+      const Quad& q = quads[w.first + g];
+      DbQuadRec t{};
+      t.jp = q.jp;
+      t.q = q.q;
+      for (int ab = 0; ab < 4; ab++) {
+        t.src[ab] = -1;
+        if (q.rec[ab] < 0) continue;
+        const UpsertRec& r = recs[(size_t)q.rec[ab]];
+        t.src[ab] = (long long)off;
+        t.len[ab] = (int)r.len;
+        if (r.len) memcpy(host.data() + bytes0 + off, r.data, r.len);
+        off += r.len;
+        const int jl = 2 * q.jp + (ab >> 1), il = 2 * q.q + (ab & 1);
+        if (patch && cell_seen.emplace((size_t)(jl >> 4) * (size_t)d.np_local + (size_t)il, 1).second) cells.push_back(PlanarPatchCell{jl, il});
+      }
+      table[g] = t;
+    }
+    memcpy(host.data(), table.data(), w.groups * sizeof(DbQuadRec));
+    if (!cells.empty()) memcpy(host.data() + cells0, cells.data(), cells.size() * sizeof(PlanarPatchCell));
+    h2d_sync(d.upload.p, host.data(), bytes0 + w.bytes);
+    DbEncodeDesc e = encode_desc(d);
+    e.win = d.upload.p + bytes0;
+    launch_db_encode_quads(D.T, e, reinterpret_cast<const DbQuadRec*>(d.upload.p), w.groups, 0);
+    if (patch)   // same stream, after the encode
+      launch_planar_patch_items(reinterpret_cast<unsigned char*>(d.planar->p), d.words.p, (int)planes, d.np_local, d.nj,
+                                reinterpret_cast<const PlanarPatchCell*>(d.upload.p + cells0), cells.size(), 0);
+    HIP_CHECK(hipDeviceSynchronize());
+  }
+}
+
+// `n` checked records in call order -> what sp_db_update_item on each in turn would leave: a later record for an index wins
+// (deduplicated here, before anything is launched; the survivors keep the order of first appearance, which is the order sequential
+// calls hand out a sparse bucket's slots in)
+void upsert_many(sp_db& d, const UpsertRec* in, size_t n) {
+  if (n == 0) return;
+  std::vector<UpsertRec> recs;
+  recs.reserve(n);
+  std::unordered_map<size_t, size_t> at;
+  at.reserve(n);
+  for (size_t i = 0; i < n; i++) {
+    auto it = at.emplace(in[i].idx, recs.size());
+    if (it.second)
+      recs.push_back(in[i]);
+    else
+      recs[it.first->second] = in[i];
+  }
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (d.sparse)
+    upsert_sparse(d, recs);
+  else
+    upsert_dense(d, recs);
+}
+// sp_db_update_item's own bounds for an entry of a list: "" when it passes, else the fault (the text is built only then)
+std::string upsert_fault(const Params& p, size_t idx, size_t len) {
+  if (idx >= p.num_items()) return "item index " + std::to_string(idx) + " out of range (num_items " + std::to_string(p.num_items()) + ")";
+  if (len > p.db_item_size) return std::to_string(len) + " item bytes, db_item_size is " + std::to_string(p.db_item_size);
+  return std::string();
+}
+
 }  // namespace
 
 SweepBatchDesc spiral::group_pass(const sp_db& db, sp_query_t* const* qs, int B, bool use_planar, PlanarPin& pin) {
@@ -621,14 +816,7 @@ int sp_db_update_item(sp_db_t* d, size_t item_idx, const uint8_t* data, size_t l
       } else {
         new_key = true;
         slot = d->slot_of.size();
-        if (slot >= d->slots_cap) {  // grow the polynomial store (amortised doubling, contents preserved)
-          const size_t cap = std::max<size_t>(64, d->slots_cap * 2);
-          DevBuf<u64> bigger(cap * poly_words);
-          if (d->slots_cap) HIP_CHECK(hipMemcpy(bigger.p, d->polys.p, d->slots_cap * poly_words * 8, hipMemcpyDeviceToDevice));
-          if (d->slots_cap && tunable("h2d_cache_sync", 0) != 0) launch_cache_sync(nullptr, 0);  // (as h2d_sync)
-          d->polys = std::move(bigger);
-          d->slots_cap = cap;
-        }
+        sparse_reserve(*d, slot + 1);  // grows the polynomial store when it is full
         if (!d->rows_dirty) {  // does the item open a new first-dimension row?  (then the pruned expansion plan changes)
           const size_t j_new = item_idx / p.num_per();
           bool row_known = false;
@@ -665,6 +853,60 @@ int sp_db_update_item(sp_db_t* d, size_t item_idx, const uint8_t* data, size_t l
       launch_planar_patch_item(reinterpret_cast<unsigned char*>(d->planar->p), d->words.p, (int)p.planes(), d->np_local, d->nj,
                                (int)j - d->j0, (int)(ii / (size_t)d->col_G), 0);
     HIP_CHECK(hipDeviceSynchronize());
+  });
+}
+
+int sp_db_update_items(sp_db_t* d, const size_t* item_idx, const uint8_t* const* data, const size_t* lens, size_t n) {
+  return guarded([&] {
+    need(d && ((item_idx && data && lens) || n == 0), "null argument");
+    check_device(d->device);
+    const Params& p = d->params->p;
+    std::vector<UpsertRec> recs(n);
+    for (size_t i = 0; i < n; i++) {   // every entry is checked before the first is written
+      if (item_idx[i] >= p.num_items() || lens[i] > p.db_item_size) throw ArgError("entry " + std::to_string(i) + ": " + upsert_fault(p, item_idx[i], lens[i]));
+      need(data[i] || lens[i] == 0, "null argument");
+      recs[i] = UpsertRec{item_idx[i], data[i], lens[i]};
+    }
+    upsert_many(*d, recs.data(), n);
+  });
+}
+
+int sp_db_update_rows(sp_db_t* d, const uint8_t* body, size_t body_len, size_t* applied, size_t* largest_update) {
+  if (applied) *applied = 0;
+  if (largest_update) *largest_update = 0;
+  return guarded([&] {
+    need(d && (body || body_len == 0), "null argument");
+    check_device(d->device);
+    const Params& p = d->params->p;
+    // update_many_items (loading.rs:361-377): be32 chunk_len | chunk = be32 item index | item bytes (update_item, :301-315)
+    auto be32 = [&](size_t at) { return ((size_t)body[at] << 24) | ((size_t)body[at + 1] << 16) | ((size_t)body[at + 2] << 8) | (size_t)body[at + 3]; };
+    std::vector<UpsertRec> recs;
+    std::string fault;
+    size_t off = 0, largest = 0;
+    while (off < body_len && fault.empty()) {
+      const size_t left = body_len - off;
+      const size_t chunk_len = left >= 4 ? be32(off) : 0;
+      if (left < 4)
+        fault = "the body ends inside its length";
+      else if (chunk_len > left - 4)
+        fault = "chunk_len " + std::to_string(chunk_len) + " but the body has " + std::to_string(left - 4) + " more bytes";
+      else if (chunk_len < 4)
+        fault = "chunk_len " + std::to_string(chunk_len) + " does not hold the item index";
+      else if (be32(off + 4) >= p.num_items() || chunk_len - 4 > p.db_item_size)
+        // item bytes 0 .. db_item_size as sp_db_update_item; the reference's bound (loading.rs:305-310) is whole chunks
+        fault = upsert_fault(p, be32(off + 4), chunk_len - 4);
+      else {
+        recs.push_back(UpsertRec{be32(off + 4), body + off + 8, chunk_len - 4});
+        largest = std::max(largest, chunk_len);
+        off += 4 + chunk_len;
+      }
+    }
+    if (!fault.empty()) fault = "/update-row record " + std::to_string(recs.size()) + " at byte offset " + std::to_string(off) + ": " + fault;
+    // the records before a faulty one are applied: the reference applies while it parses
+    upsert_many(*d, recs.data(), recs.size());
+    if (applied) *applied = recs.size();
+    if (largest_update) *largest_update = largest;
+    if (!fault.empty()) throw ArgError(fault + " (" + std::to_string(recs.size()) + " records applied)");
   });
 }
 

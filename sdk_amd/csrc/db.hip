@@ -243,6 +243,120 @@ void launch_db_encode(const DevTables& T, const DbEncodeDesc& d, hipStream_t s) 
   launched(0, "k_db_encode");
 }
 
+// ---- k_db_encode's only_item mode driven by a list (sp_db_update_items) -- grid (n_quads * planes), (quad, plane) flattened along x
+// A workgroup owns one touched quad of one plane: the items the list gives bytes for are re-encoded (update_item_raw,
+// loading.rs:317-359: the record zero padded to db_item_size, so chunk `plane` is bytes [plane * bytes_per_chunk, ...) of it cut at
+// db_item_size), the others keep their resident words, and the quad is written once -- in the PACKED format its four words are one
+// 28-byte lane group, which is why two updated items of one quad must not be two workgroups'.  (Its own body beside k_db_encode's,
+// which stays as it was compiled.)
+__device__ __forceinline__ u32 quad_item_coeff(const DbEncodeDesc& d, const uint8_t* bytes, int len, int chunk_idx, int z) {
+  const int pos = chunk_idx * d.bytes_per_chunk;
+  if (pos >= d.db_item_size) return 0u;
+  const int avail = d.db_item_size - pos;
+  const int bytes_read = avail < d.bytes_per_chunk ? avail : d.bytes_per_chunk;
+  const int words_read = (bytes_read * 8 + d.logp - 1) / d.logp;
+  if (z >= words_read) return 0u;
+  const int bit = z * d.logp;
+  const int b0 = bit >> 3, sh = bit & 7;
+  u64 acc = 0;
+  const int nb = (sh + d.logp + 7) >> 3;
+  for (int i = 0; i < nb; i++) {
+    const int bi = b0 + i;
+    const u64 byte = (bi < bytes_read && pos + bi < len) ? (u64)bytes[pos + bi] : 0ULL;
+    acc |= byte << (8 * i);
+  }
+  return (u32)((acc >> sh) & ((1ULL << d.logp) - 1ULL));
+}
+__global__ __launch_bounds__(256) void k_db_encode_quads(DevTables T, DbEncodeDesc d, const DbQuadRec* quads) {
+  __shared__ u32 lds0[LDS_WORDS];
+  __shared__ u32 lds1[LDS_WORDS];
+  const int tau = threadIdx.x;
+  const int plane = (int)(blockIdx.x % (unsigned)d.planes);
+  const DbQuadRec* qr = quads + blockIdx.x / (unsigned)d.planes;
+  const int jp = qr->jp, qd = qr->q;
+  const int chunks = d.num_per >> 7, npairs = d.nj >> 1;
+  u64 w[4][8];  // [row a * 2 + ii b][k]: words at z = 8 tau + k (statically indexed only: they stay in registers)
+#pragma unroll
+  for (int t = 0; t < 4; t++)
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[t][k] = 0;
+  u32* la = lds0;
+  u32* lb = lds1;
+#pragma unroll 1
+  for (int ab = 0; ab < 4; ab++) {
+    const int a = ab >> 1, b = ab & 1;
+    const int jl = 2 * jp + a, ii = 2 * qd + b;
+    const bool valid = jl < d.nj && ii < d.num_per;
+    const long long src = qr->src[ab];
+    u64 cur[8];
+    if (src < 0 || !valid) {
+      // keep the neighbour's resident words of the lane group (8-byte words are stored one by one: a kept one is neither read
+      // nor written)
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        cur[k] = 0;
+        if (valid && d.packed) {
+          const u32* unit = reinterpret_cast<const u32*>(d.db) + packed_unit_offset((size_t)plane * N + 8 * tau + k, jp, ii >> 7, npairs, chunks);
+          cur[k] = unpack_word(unit, (ii & 127) >> 1, ab);
+        }
+      }
+    } else {
+      const uint8_t* bytes = d.win + src;
+      const int len = qr->len[ab];
+      u32 lo[8];
+#pragma unroll 1
+      for (int c = 0; c < 2; c++) {
+        const ModConst m = T.c.mod[c];
+        u32 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          const u32 x = quad_item_coeff(d, bytes, len, plane, tau + 256 * k);
+          // recenter_mod(x, p, Q) reduced mod q_c: values above p/2 are negative
+          v[k] = x > d.pt_modulus / 2 ? m.q - (d.pt_modulus - x) : x;
+        }
+        const u32* fw = T.tw + (size_t)c * 4 * N;
+        ntt_fwd_block(v, tau, la, lb, fw, fw + N, m.q, m.two_q);
+        {
+          u32* tmp = la;
+          la = lb;
+          lb = tmp;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+          if (c == 0)
+            lo[k] = v[k];
+          else
+            cur[k] = (u64)lo[k] | ((u64)v[k] << 32);
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+      for (int k = 0; k < 8; k++) w[t][k] = t == ab ? cur[k] : w[t][k];
+  }
+  const int jl0 = 2 * jp, ii0 = 2 * qd;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int z = 8 * tau + k;
+    if (d.packed) {
+      u32* unit = reinterpret_cast<u32*>(d.db) + packed_unit_offset((size_t)plane * N + z, jp, ii0 >> 7, npairs, chunks);
+      pack_unit_lane(unit, (ii0 & 127) >> 1, w[0][k], w[1][k], w[2][k], w[3][k]);
+    } else {
+#pragma unroll
+      for (int ab = 0; ab < 4; ab++) {
+        const int jl = jl0 + (ab >> 1), ii = ii0 + (ab & 1);
+        if (qr->src[ab] >= 0 && jl < d.nj && ii < d.num_per) d.db[(((size_t)plane * N + z) * d.nj + jl) * d.num_per + ii] = w[ab][k];
+      }
+    }
+  }
+}
+void launch_db_encode_quads(const DevTables& T, const DbEncodeDesc& d, const DbQuadRec* quads, size_t n_quads, hipStream_t s) {
+  if (n_quads == 0) return;   // (n_quads * planes <= UPSERT_MAX_GROUP_PLANES = 2^23: the caller cuts its windows there)
+  hipLaunchKernelGGL(k_db_encode_quads, dim3((unsigned)(n_quads * (size_t)d.planes)), dim3(256), 0, s, T, d, quads);
+  launched(0, "k_db_encode_quads");
+}
+
 // caller-owned query words of the stage export (sp_multiply_reg_by_database): both limbs reduced in place, as
 // k_interleave_query reduces the wire words of a direct-upload query
 __global__ __launch_bounds__(256) void k_canon_words(u64* w, size_t total) {

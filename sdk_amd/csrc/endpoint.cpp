@@ -2,6 +2,8 @@
 // process_query, without the HTTP transport.
 //   ServerState            lib/server/src/bin/server.rs:21-28   params + database + RwLock<HashMap<uuid, PublicParameters>>
 //   POST /setup            bin/server.rs:71-94    JSON string of base64(public parameters) -> {"uuid":"..."}
+//   POST /update-row       bin/server.rs:31-43    raw body of be32 chunk_len | be32 item index | item bytes records, applied under the
+//                                                  write side of RwLock<SparseDb> (:24,35) -> sp_db_update_rows: one launch per window
 //   POST /private-read     bin/server.rs:98-164   JSON list of base64 requests; request = uuid (36 bytes) || query when the
 //                                                  params expand queries, public parameters || query otherwise; the
 //                                                  reference answers them one by one (:152-158) -- here the list goes
@@ -10,6 +12,7 @@
 // what serde_json / the base64 crate emit) is plain host code.
 #include <array>
 #include <cerrno>
+#include <chrono>
 #include <cstring>
 #include <sys/random.h>
 #include <memory>
@@ -172,6 +175,8 @@ struct sp_server {
   bool expand_queries = true;
   mutable std::shared_mutex mu;  // bin/server.rs:26 RwLock<HashMap<String, PublicParameters>>
   std::unordered_map<std::string, std::shared_ptr<sp_pp_t>> pub_params;
+  // bin/server.rs:24 RwLock<SparseDb>: /private-read holds it shared for its whole list (:102), /update-row exclusively (:35)
+  mutable std::shared_mutex db_mu;
 };
 
 template <typename F>
@@ -311,6 +316,7 @@ int sp_server_private_read(sp_server_t* s, const uint8_t* const* requests, const
                            size_t out_stride, size_t* out_lens) {
   return guarded_ep([&] {
     if (!s || n < 0 || (n > 0 && (!requests || !request_lens || !out || !out_lens))) throw Fail{SP_E_ARG, "null argument"};
+    std::shared_lock<std::shared_mutex> db_lk(s->db_mu);
     private_read(*s, requests, request_lens, n, out, out_stride, out_lens);
   });
 }
@@ -336,6 +342,7 @@ int sp_server_private_read_json(sp_server_t* s, const char* body, size_t body_le
     }
     std::vector<uint8_t> resp((size_t)n * s->response_bytes);
     std::vector<size_t> rl((size_t)n, 0);
+    std::shared_lock<std::shared_mutex> db_lk(s->db_mu);
     private_read(*s, reqs.data(), lens.data(), n, resp.data(), s->response_bytes, rl.data());
     std::string js = "[";  // serde_json::to_string(&Vec<String>)
     for (int i = 0; i < n; i++) {
@@ -348,6 +355,27 @@ int sp_server_private_read_json(sp_server_t* s, const char* body, size_t body_le
     if (js.size() + 1 > out_cap) throw Fail{SP_E_ARG, "output buffer too small (see sp_server_private_read_json_bound)"};
     memcpy(out, js.c_str(), js.size() + 1);
     *out_len = js.size();
+  });
+}
+
+int sp_server_update_row(sp_server_t* s, sp_db_t* db, const uint8_t* body, size_t body_len, char* out, size_t out_cap, size_t* out_len) {
+  return guarded_ep([&] {
+    if (!s || !db || (!body && body_len) || !out || !out_len) throw Fail{SP_E_ARG, "null argument"};
+    if (db != s->db) throw Fail{SP_E_ARG, "/update-row: db is not the handle this server was created on"};
+    const auto t0 = std::chrono::steady_clock::now();
+    size_t applied = 0, largest = 0;
+    {
+      std::unique_lock<std::shared_mutex> db_lk(s->db_mu);  // bin/server.rs:35 data.db.write()
+      const int rc = sp_db_update_rows(db, body, body_len, &applied, &largest);
+      if (rc != SP_OK) throw Fail{rc, sp_last_error()};
+    }
+    const long long us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    // bin/server.rs:38-42 format!
+    const std::string resp = "{\"status\":\"done updating\", \"loading_time_us\":" + std::to_string(us) + ", \"largest_update\":" +
+                             std::to_string(largest) + "}";
+    if (resp.size() + 1 > out_cap) throw Fail{SP_E_ARG, "output buffer too small"};
+    memcpy(out, resp.c_str(), resp.size() + 1);
+    *out_len = resp.size();
   });
 }
 

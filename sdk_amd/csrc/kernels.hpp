@@ -424,6 +424,18 @@ size_t sweep_planar_bytes(int planes, int num_per, int nj);
 void launch_packed_to_planar(unsigned char* planar, const u64* packed, int planes, int num_per, int nj, hipStream_t s);
 // ... and the 8 entries per (plane, z) that hold one item (local row j, local column ii), after sp_db_update_item
 void launch_planar_patch_item(unsigned char* planar, const u64* packed, int planes, int num_per, int nj, int j, int ii, hipStream_t s);
+// A bulk upsert (sp_db_update_items) sends at most UPSERT_MAX_GROUP_PLANES / planes encode groups (a sparse bucket's items, a dense
+// database's touched quads) per launch.  The encode launches then have groups * planes <= 2^23 workgroups; a quad touches at most
+// two patch cells (its two rows share a 16-row group), and a cell takes planes * N * 8 / 256 = 64 * planes blocks of the patch
+// launch: at most 2 * 2^23 * 64 = 2^30.  All below the 2^31 - 1 blocks of grid.x.
+constexpr size_t UPSERT_MAX_GROUP_PLANES = (size_t)1 << 23;
+// ... and the list form, after sp_db_update_items: entry `e` of `cells` (device memory) names one column of one 16-row group (any local
+// row j of the group, local column ii); the caller lists every touched (j >> 4, ii) once, so no planar entry is written twice
+struct PlanarPatchCell {
+  int j, ii;
+};
+void launch_planar_patch_items(unsigned char* planar, const u64* packed, int planes, int num_per, int nj, const PlanarPatchCell* cells,
+                               size_t n_cells, hipStream_t s);
 void launch_sweep_planar(const DevTables& T, const SweepBatchDesc& d, hipStream_t s);   // sweep_planar.hip
 // does this shape / group size run on the matrix cores (switch batch_mfma, default on from batch_mfma_min = 4 queries)?
 // Groups of more than SWEEP_BATCH_MAX queries exist only there.
@@ -480,11 +492,32 @@ struct DbEncodeDesc {
   ColMap cm;              // num_per above is the LOCAL column count
 };
 void launch_db_encode(const DevTables& T, const DbEncodeDesc& d, hipStream_t s);
+// The list-driven form of the single-item update (sp_db_update_items): one workgroup per (touched quad, plane).  Entry `e` of `quads`
+// (device memory) names the quad (local row pair jp, local column pair q) and, for each of its four items [row a * 2 + column b], the
+// byte offset of the item's new bytes in d.win and their count (<= db_item_size, the rest reads as zero), or src = -1: keep the
+// resident word.  The four words of a quad share one 28-byte lane group of the PACKED format, so the caller lists a quad ONCE with
+// every item of it that the call updates.  Of `d`, win is the base the src offsets count from; win_item0, win_bytes, file_len,
+// jp0 / njp and only_* are not read.
+struct DbQuadRec {
+  int jp, q;
+  int len[4];
+  long long src[4];
+};
+void launch_db_encode_quads(const DevTables& T, const DbEncodeDesc& d, const DbQuadRec* quads, size_t n_quads, hipStream_t s);
 
 // ---- sparse buckets (lib/server SparseDb caller; sparse.hip) ----------------------------------------------------------
 // one item's bytes (device) -> `planes` packed NTT polynomials at slot_polys[plane][z]
 void launch_sparse_item_encode(const DevTables& T, const uint8_t* bytes, int item_bytes, int bytes_per_chunk, int logp,
                                u32 pt_modulus, u64* slot_polys, int planes, hipStream_t s);
+// ... and n_items of them in one launch (sp_db_update_items): entry `e` of `items` (device memory) gives the byte offset of the item's
+// bytes in `win`, their count (<= item_bytes, the rest reads as zero) and the slot of `polys` that receives its `planes` polynomials.
+// The caller lists a slot once.
+struct SparseItemRec {
+  unsigned long long off;
+  int len, slot;
+};
+void launch_sparse_items_encode(const DevTables& T, const uint8_t* win, const SparseItemRec* items, size_t n_items, int item_bytes,
+                                int bytes_per_chunk, int logp, u32 pt_modulus, u64* polys, int planes, hipStream_t s);
 // first-dimension multiply over the present items only (CSR by column); v = expanded NTT ciphertexts, row j at
 // ct index first + step * j; out = sweep-native [plane][r][crt][z][ii]
 void launch_sweep_sparse(const DevTables& T, const int* col_ptr, const int* col_rows, const int* col_slots, const u64* polys,

@@ -58,6 +58,65 @@ void launch_sparse_item_encode(const DevTables& T, const uint8_t* bytes, int ite
   launched(0, "k_sparse_item_encode");
 }
 
+// ---- update_many_items (loading.rs:361-377): k_sparse_item_encode with the item as a grid dimension -------------------
+// grid (n_items * planes): (item, plane) flattened along x, the item count being unbounded.  Item e's bytes are items[e].len bytes at
+// win + items[e].off (not padded: what lies past them reads as zero, which is what the single-item form finds in its zero-padded
+// upload), its polynomials go to slot items[e].slot.  The arithmetic is k_sparse_item_encode's.
+__global__ __launch_bounds__(256) void k_sparse_items_encode(DevTables T, const uint8_t* win, const SparseItemRec* items, int planes,
+                                                             int item_bytes, int bytes_per_chunk, int logp, u32 pt_modulus, u64* polys) {
+  __shared__ u32 lds0[LDS_WORDS];
+  __shared__ u32 lds1[LDS_WORDS];
+  const int tau = threadIdx.x, plane = (int)(blockIdx.x % (unsigned)planes);
+  const SparseItemRec it = items[blockIdx.x / (unsigned)planes];
+  const uint8_t* bytes = win + it.off;
+  u64* slot_polys = polys + (size_t)it.slot * planes * N;
+  const int pos = plane * bytes_per_chunk;
+  const int avail = item_bytes - pos;
+  const int bytes_read = avail < 0 ? 0 : (avail < bytes_per_chunk ? avail : bytes_per_chunk);
+  const int words_read = (bytes_read * 8 + logp - 1) / logp;
+  const int have = it.len - pos;   // bytes of this chunk that the record carries (<= 0: none)
+  u32 coeff[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int z = tau + 256 * k;
+    u32 x = 0;
+    if (z < words_read) {
+      const int bit = z * logp, b0 = bit >> 3, sh = bit & 7, nb = (sh + logp + 7) >> 3;
+      u64 acc = 0;
+      for (int i = 0; i < nb; i++) acc |= (u64)(b0 + i < bytes_read && b0 + i < have ? bytes[pos + b0 + i] : 0) << (8 * i);
+      x = (u32)((acc >> sh) & ((1ULL << logp) - 1ULL));
+    }
+    coeff[k] = x;
+  }
+  u32 lo[8];
+  u32* la = lds0;
+  u32* lb = lds1;
+#pragma unroll 1
+  for (int c = 0; c < 2; c++) {
+    const ModConst m = T.c.mod[c];
+    u32 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) v[k] = coeff[k] > pt_modulus / 2 ? m.q - (pt_modulus - coeff[k]) : coeff[k];
+    const u32* fw = T.tw + (size_t)c * 4 * N;
+    if (c == 1) __syncthreads();
+    ntt_fwd_block(v, tau, la, lb, fw, fw + N, m.q, m.two_q);
+    if (c == 0) {
+#pragma unroll
+      for (int k = 0; k < 8; k++) lo[k] = v[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; k++) slot_polys[(size_t)plane * N + 8 * tau + k] = (u64)lo[k] | ((u64)v[k] << 32);
+    }
+  }
+}
+void launch_sparse_items_encode(const DevTables& T, const uint8_t* win, const SparseItemRec* items, size_t n_items, int item_bytes,
+                                int bytes_per_chunk, int logp, u32 pt_modulus, u64* polys, int planes, hipStream_t s) {
+  if (n_items == 0) return;   // (n_items * planes <= UPSERT_MAX_GROUP_PLANES = 2^23: the caller cuts its windows there)
+  hipLaunchKernelGGL(k_sparse_items_encode, dim3((unsigned)(n_items * (size_t)planes)), dim3(256), 0, s, T, win, items, planes,
+                     item_bytes, bytes_per_chunk, logp, pt_modulus, polys);
+  launched(0, "k_sparse_items_encode");
+}
+
 // ---- multiply_reg_by_sparse_database (dot_product.rs:13-220) ----------------------------------------------------------
 // grid (num_per, planes); thread tau owns z = tau + 256 k.  Column ii's present items are col_rows / col_slots
 // [col_ptr[ii], col_ptr[ii+1]); item polynomials: polys[slot][plane][z] (lo | hi << 32); the query is read from the

@@ -95,6 +95,33 @@ void launch_planar_patch_item(unsigned char* planar, const u64* packed, int plan
                      reinterpret_cast<const u32*>(packed), zps, num_per, nj, j, ii);
   launched(0, "k_planar_patch_item");
 }
+// sp_db_update_items: the list form.  cells[e] = (local row j, local column ii) stands for the column's 16-row group j >> 4, whose 16
+// bytes per (plane, z, modulus c, digit a) are ONE entry: thread (e, zp, c, a) regathers it from the words the encode launch before it
+// on the stream has written.  The caller lists a (j >> 4, ii) once, so no entry has two writers.
+__global__ __launch_bounds__(256) void k_planar_patch_items(unsigned char* planar, const u32* packed, size_t zps, int num_per, int nj,
+                                                            const PlanarPatchCell* cells, size_t n_cells) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t per = zps * 8;
+  if (t >= n_cells * per) return;
+  const PlanarPatchCell cell = cells[t / per];
+  const size_t r = t % per;
+  const size_t zp = r >> 3;
+  const int c = (int)((r >> 2) & 1), a = (int)(r & 3);
+  const int j = cell.j, ii = cell.ii;
+  const int chunks = num_per >> 7, blocks = nj >> 6;
+  const int chunk = ii >> 7, col = ii & 127, slot = col >> 1, e = col & 1, g = slot >> 4, n = slot & 15;
+  const int block = j >> 6, kb = (j & 63) >> 4;
+  const size_t idx = planar_operand_offset(zp, chunk, g, block, e, c, a, chunks, blocks) / 16 + (size_t)(16 * kb + n);
+  reinterpret_cast<mf_u32x4_t*>(planar)[idx] = planar_gather_entry(packed, idx, num_per, nj);
+}
+void launch_planar_patch_items(unsigned char* planar, const u64* packed, int planes, int num_per, int nj, const PlanarPatchCell* cells,
+                               size_t n_cells, hipStream_t s) {
+  if (n_cells == 0) return;
+  const size_t zps = (size_t)planes * N;   // (n_cells * 64 * planes <= 2^30 blocks: see UPSERT_MAX_GROUP_PLANES)
+  hipLaunchKernelGGL(k_planar_patch_items, dim3((unsigned)((n_cells * zps * 8 + 255) / 256)), dim3(256), 0, s, planar,
+                     reinterpret_cast<const u32*>(packed), zps, num_per, nj, cells, n_cells);
+  launched(0, "k_planar_patch_items");
+}
 // the 9 .. 16-query pass over the planar copy: 3.47 ms per C2 plane against 4.19 for k_sweep_mfma_batch<8, 1, 0, 2> on the PACKED
 // words (scripts/ubench/mfma_planar.hip, profiles/r05_mfma_planar.md); eight waves per workgroup share the z-row's query planes
 // where the workgroup has two chunks to split, units of the load ring as the row count allows

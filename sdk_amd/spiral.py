@@ -437,6 +437,30 @@ class Database:
         _chk(lib().sp_db_update_item(_vp(self.h), C.c_size_t(item_idx), _p(b, u8p), C.c_size_t(b.size)))
         return self
 
+    def update_items(self, pairs):
+        """upsert the (item index, bytes) pairs in one call (sp_db_update_items): what update_item on each pair in order leaves,
+        a later pair for an index winning"""
+        pairs = [(int(i), np.frombuffer(bytes(d), dtype=np.uint8)) for i, d in pairs]
+        n = len(pairs)
+        idx = (C.c_size_t * max(n, 1))(*[i for i, _ in pairs])
+        ptr = (u8p * max(n, 1))(*[_p(b, u8p) for _, b in pairs])
+        lens = (C.c_size_t * max(n, 1))(*[b.size for _, b in pairs])
+        _chk(lib().sp_db_update_items(_vp(self.h), idx, ptr, lens, C.c_size_t(n)))
+        return self
+
+    def update_rows(self, body):
+        """the body of POST /update-row (lib/server update_many_items, db/loading.rs:361-377: records be32 chunk_len | be32 item
+        index | item bytes) -> (records applied, largest chunk_len).  A faulty record raises SpiralError after the records before
+        it have been applied; the exception's `applied` is their count."""
+        b = np.frombuffer(bytes(body), dtype=np.uint8)
+        applied, largest = C.c_size_t(0), C.c_size_t(0)
+        rc = lib().sp_db_update_rows(_vp(self.h), _p(b, u8p), C.c_size_t(b.size), C.byref(applied), C.byref(largest))
+        if rc != 0:
+            e = SpiralError(f"libspiral_hip rc={rc}: {_err()}")
+            e.rc, e.applied = rc, int(applied.value)
+            raise e
+        return int(applied.value), int(largest.value)
+
     def fill_synthetic(self, seed):
         _chk(lib().sp_db_fill_synthetic(_vp(self.h), C.c_uint64(seed)))
         return self
@@ -757,8 +781,8 @@ def encode(params, v_packed_ct):
 
 # ------------------------------------------------------------------------------------------------
 class Server:
-    """ServerState of lib/server/src/bin/server.rs:21-28 without the HTTP transport (sp_server_*): POST /setup and POST
-    /private-read bodies in, response bodies out; public parameters stay device resident per client uuid and a list of
+    """ServerState of lib/server/src/bin/server.rs:21-28 without the HTTP transport (sp_server_*): POST /setup, POST /update-row and
+    POST /private-read bodies in, response bodies out; public parameters stay device resident per client uuid and a list of
     queries goes through the batch scheduler (<= 16 queries per pass over the database)."""
 
     def __init__(self, params, db):
@@ -811,6 +835,15 @@ class Server:
         l_arr = (C.c_size_t * max(n, 1))(*[b.size for b in bufs])
         _chk(lib().sp_server_private_read(_vp(self.h), r_arr, l_arr, C.c_int(n), _p(out, u8p), C.c_size_t(rb), lens))
         return [out[i * rb:i * rb + lens[i]].tobytes() for i in range(n)]
+
+    def update_row(self, body):
+        """/update-row on the HTTP body (bin/server.rs:31-43), applied to the server's database under the write side of its lock
+        -> '{"status":"done updating", "loading_time_us":N, "largest_update":M}'"""
+        b = np.frombuffer(bytes(body), dtype=np.uint8)
+        out = C.create_string_buffer(128)
+        n = C.c_size_t(0)
+        _chk(lib().sp_server_update_row(_vp(self.h), _vp(self.db.h), _p(b, u8p), C.c_size_t(b.size), out, C.c_size_t(128), C.byref(n)))
+        return out.raw[:n.value].decode()
 
     def private_read_json(self, body):
         """/private-read on the HTTP body (JSON list of base64 strings) -> JSON list of base64 strings"""
