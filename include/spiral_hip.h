@@ -184,7 +184,10 @@ int sp_process_query(const sp_params_t*, const sp_pp_t*, const uint8_t* query, s
  * queries share database passes in groups -- up to 8 per pass, up to 16 where the two-tile matrix-core pass applies (which
  * reads the digit-planar copy of the database when one stands: sp_db_prepare_batch) -- with the next group's expansions
  * queued behind the current group's folds; on 8-byte (narrow) databases it is one pass per query with up to three queries
- * in flight on their own streams.  On a sparse bucket (sp_db_create_sparse) the list is cut into groups of at most 8, and a
+ * in flight on their own streams -- except that on an unsharded 8-byte database with 2 <= num_per <= 64 the list is cut into groups
+ * of 8 and a group of at least `narrow_batch_min` members (sp_debug_set / SPIRAL_NARROW_BATCH_MIN; shipped 0, 0 = never, negative =
+ * the shipped value) takes the PACKED flow with ONE pass over the database (k_sweep_narrow_batch), a last group below the threshold and
+ * a trailing single query staying per query.  On a sparse bucket (sp_db_create_sparse) the list is cut into groups of at most 8, and a
  * group of at least `sparse_batch_min` members (sp_debug_set / SPIRAL_SPARSE_BATCH_MIN; shipped 2, 0 = never, negative = the shipped value) shares ONE pass over the
  * bucket's present items under one snapshot of its index, each member with its own pruned expansion and its own fold; smaller
  * groups and a trailing single query are answered per query as on 8-byte databases.  Out of memory is handled inside the call (the planar copy is given back, then groups of
@@ -377,7 +380,8 @@ int sp_bench_sweep_ex(sp_query_t* q, const sp_db_t* db, int iters, int per_plane
  * share database passes exactly as a group of sp_process_query_batch does (query digit table + k_sweep_mfma_batch on
  * the matrix cores from 4 queries, k_sweep_packed_batch below; one launch over all planes); returns average
  * milliseconds per PASS.  The queries' partial buffers hold the pass's outputs afterwards.  On a sparse bucket: the group's
- * one pass (k_sweep_sparse_batch) for 1 .. 8 queries begun for that bucket (sp_query_begin_for_db) on one snapshot of its index. */
+ * one pass (k_sweep_sparse_batch) for 1 .. 8 queries begun for that bucket (sp_query_begin_for_db) on one snapshot of its index;
+ * an unsharded 8-byte database with 2 <= num_per <= 64: the group's one pass (k_sweep_narrow_batch) for 2 .. 8 begun queries. */
 int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, int iters, float* ms_per_pass);
 /* ... and for the pass of sp_query_sweep_scatter_group over a row shard (queries begun for it): layout 1 = the scatter-form
  * pass as the group call launches it, 0 = the existing one-tile pass over the same rows writing the plain [z][ii] layout

@@ -285,6 +285,7 @@ SweepBatchDesc spiral::group_pass(const sp_db& db, sp_query_t* const* qs, int B,
     d.qv[i] = qs[i]->ws->qv.p;
     d.out[i] = qs[i]->ws->sweep_out.p;
   }
+  d.narrow = !db.packed;   // the 8-byte layout: callers come here only where sweep_narrow_batch_shape_ok holds
   if (sweep_batch_wants_mfma(d)) {
     W0.batch_rq.ensure(sweep_batch_rq_words(d.nj, sweep_batch_tiles(d.batch)));
     d.rq = W0.batch_rq.p;
@@ -568,7 +569,7 @@ const char* sp_path_name(int bit) {
                                 "rccl_in_library", "fold_wave", "cu_split_overlap", "expand_split", "pipe_class_split",
                                 "sweep_batch_mfma", "custom_transport", "from_sweep_wave",
                                 "fold_tail_batched", "sweep_ring", "sweep_batch_mfma_two_tiles", "fold_wave8", "sweep_batch_planar",
-                                "expand_group", "expand_wave", "sweep_batch_scatter", "sparse_group_pass"};
+                                "expand_group", "expand_wave", "sweep_batch_scatter", "sparse_group_pass", "sweep_narrow_group"};
   return bit >= 0 && bit < (int)(sizeof(names) / sizeof(names[0])) ? names[bit] : nullptr;
 }
 

@@ -125,20 +125,24 @@ struct GroupsInFlight {
   }
 };
 
-// PACKED databases.  Groups of up to 8 queries -- 16 where the two-tile matrix-core pass applies (batch_group = 0, the default, asks
+// PACKED databases, and narrow ones (below).  Groups of up to 8 queries -- 16 where the two-tile matrix-core pass applies (batch_group = 0, the default, asks
 // the kernel side; a positive value caps the group) -- share one database pass.  Nothing waits for a group's folds before the next
 // group's expansions and pass are queued (the passes themselves run one after the other: both are HBM-bound), and at
 // most two groups hold workspaces at a time.  Measured at C2 (profiles/r02_fold_batch_experiments.md): the overlap
 // buys nothing yet -- 16 queries take 2 x the time of 8, and 8 as 2 x 4 are slower (195 vs 236 queries/s) -- because
 // the batched sweep's workgroups fill every CU's register file, so a fold wave only starts when the pass drains.
+// Narrow databases (8-byte words, 2 <= num_per <= 64: sweep_narrow_batch_shape_ok) take the same flow with k_sweep_narrow_batch as
+// the pass: groups of 8, and only groups of at least `narrow_min` members (switch narrow_batch_min) -- what is left of the list,
+// a last group below the threshold or a trailing single query, is answer_in_flight's.
 struct GroupedFlow : GroupsInFlight {
   // diagnostic (switch batch_trace): host time stamps of this call's phases on stderr, microseconds from entry
   const bool trace = tunable("batch_trace", 0) != 0;
   int start = 0;   // first query not yet answered (a retry after an out-of-memory resumes here)
   bool use_planar = true, one_group = false;   // what the out-of-memory ladder gives up, in this order
   int group_max = 0;
+  const int narrow_min;   // > 0: a narrow database; groups below this size are not this flow's
 
-  explicit GroupedFlow(const BatchArgs& args) : GroupsInFlight(args) {}
+  explicit GroupedFlow(const BatchArgs& args, int narrow_group_min = 0) : GroupsInFlight(args), narrow_min(narrow_group_min) {}
 
   void stamp(const char* what) const {
     if (trace)
@@ -153,6 +157,7 @@ struct GroupedFlow : GroupsInFlight {
     group_max = (int)tunable("batch_group", 0);
     if (group_max <= 0) group_max = shape_max;
     group_max = std::max(1, std::min(shape_max, group_max));
+    if (narrow_min > 0) group_max = SWEEP_BATCH_MAX;
     if (group_max > SWEEP_BATCH_MAX && a.batch > SWEEP_BATCH_MAX) {
       // two groups of 16 hold up to 32 workspaces: keep to groups of 8 when the device could not hold them beside the database
       size_t fr = 0, tot = 0;
@@ -225,7 +230,7 @@ struct GroupedFlow : GroupsInFlight {
 
   void run_groups() {   // the list from `start` on
     check_device(a.db->device);
-    for (int g0 = start; g0 < a.batch; g0 += group_max) {
+    for (int g0 = start; a.batch - g0 >= std::max(1, narrow_min); g0 += group_max) {
       const int B = std::min(group_max, a.batch - g0);
       if (one_group) {
         if (!all_qs.empty()) drain(all_qs.size());                        // nothing in flight beside this group
@@ -274,7 +279,7 @@ struct GroupedFlow : GroupsInFlight {
     int rc = guarded([&] { run_groups(); });
     // Out of memory (the hipMemGetInfo estimates above are rough): give up, one after the other, what only makes the call faster, and
     // answer the REST of the list each time -- responses already copied out stay.
-    for (int step = 1; rc == SP_E_OOM && step <= 3; step++) {
+    for (int step = narrow_min > 0 ? 2 : 1; rc == SP_E_OOM && step <= 3; step++) {   // (a narrow database has no planar copy)
       abandon();
       (void)hipGetLastError();
       start = (int)drained;
@@ -283,18 +288,36 @@ struct GroupedFlow : GroupsInFlight {
       else if (give_up(step))
         rc = guarded([&] { run_groups(); });
     }
-    return rc != SP_OK ? fail(rc) : rc;
+    if (rc != SP_OK) return fail(rc);
+    if ((int)drained == a.batch) return SP_OK;
+    BatchArgs rest = a;   // narrow: a last group below the threshold keeps the per-query flow
+    rest.pps += drained;
+    rest.queries += drained;
+    rest.query_lens += drained;
+    rest.batch -= (int)drained;
+    rest.out += drained * a.out_stride;
+    return answer_in_flight(rest);
   }
 };
 
-int answer_in_groups(const BatchArgs& a) {
+int answer_in_groups(const BatchArgs& a, int narrow_min = 0) {
   if (a.out_stride < a.h->p.response_bytes()) {
     sp_set_last_error_("out_stride smaller than response_bytes");
     return SP_E_ARG;
   }
   // the questions of the flow (LDS opt-in limit, free memory) are put to the CURRENT device: it has to be the database's
   const int rc = guarded([&] { check_device(a.db->device); });
-  return rc != SP_OK ? rc : GroupedFlow(a).run();
+  return rc != SP_OK ? rc : GroupedFlow(a, narrow_min).run();
+}
+
+// dense, unsharded 8-byte databases: the group flow where the shape is k_sweep_narrow_batch's and the list reaches the threshold
+int answer_narrow(const BatchArgs& a) {
+  long m = tunable("narrow_batch_min", NARROW_BATCH_MIN_DEFAULT);
+  if (m < 0) m = NARROW_BATCH_MIN_DEFAULT;   // (a negative value: the shipped default again, for a caller that had overridden it)
+  const int group_min = (int)std::max(2L, m);
+  if (m <= 0 || group_min > SWEEP_BATCH_MAX || a.batch < group_min || !sweep_narrow_batch_shape_ok(a.db->np_local, a.db->nj))
+    return answer_in_flight(a);
+  return answer_in_groups(a, group_min);
 }
 
 
@@ -402,5 +425,7 @@ extern "C" int sp_process_query_batch(const sp_params_t* h, const sp_pp_t* const
   const BatchArgs a{h, pps, queries, query_lens, batch, db, out, out_stride, out_len, std::chrono::steady_clock::now()};
   const bool batched = db->packed && db->num_shards == 1 && db->col_G == 1 && !tunable("no_batch_sweep", 0);
   if (db->sparse) return answer_sparse(a);
-  return batched ? answer_in_groups(a) : answer_in_flight(a);
+  if (batched) return answer_in_groups(a);
+  const bool narrow = !db->packed && db->num_shards == 1 && db->col_G == 1 && !tunable("no_batch_sweep", 0);
+  return narrow ? answer_narrow(a) : answer_in_flight(a);
 }

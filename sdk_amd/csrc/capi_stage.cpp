@@ -110,7 +110,10 @@ int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, in
       return;
     }
     need(qs && db && ms_per_pass && iters > 0 && batch >= 1 && batch <= sweep_batch_group_max(db ? db->np_local : 0, db ? db->nj : 0), "bad argument");
-    need(db->packed && db->num_shards == 1 && db->col_G == 1, "the batched pass needs an unsharded PACKED database");
+    // ... or an unsharded narrow one (8-byte words, 2 <= num_per <= 64) for 2 .. 8 queries: the group's one pass, k_sweep_narrow_batch
+    // (a single query is never a group there: it is refused as on every other 8-byte database)
+    const bool narrow = !db->packed && db->num_shards == 1 && db->col_G == 1 && batch >= 2 && sweep_narrow_batch_shape_ok(db->np_local, db->nj);
+    need(narrow || (db->packed && db->num_shards == 1 && db->col_G == 1), "the batched pass needs an unsharded PACKED database");
     check_device(db->device);
     for (int i = 0; i < batch; i++) {
       need(qs[i] && qs[i]->state >= 1, "query not begun");

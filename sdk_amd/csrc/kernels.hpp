@@ -80,7 +80,8 @@ enum PathBit : u64 {
   PATH_EXPAND_GROUP = 1ull << 32,     // a group's expansions with every round's launches shared (grid dimension = query; r06)
   PATH_EXPAND_WAVE = 1ull << 33,      // k_expand_wave: a round's many-digit side on the wave-per-transform NTT (r06)
   PATH_SWEEP_BATCH_SCATTER = 1ull << 34,// k_sweep_mfma_scatter: the one-tile batched pass over a row shard, reduce-scatter layout
-  PATH_SWEEP_SPARSE_GROUP = 1ull << 35  // k_sweep_sparse_batch: one pass over a sparse bucket for a group of up to 8 queries
+  PATH_SWEEP_SPARSE_GROUP = 1ull << 35, // k_sweep_sparse_batch: one pass over a sparse bucket for a group of up to 8 queries
+  PATH_SWEEP_NARROW_GROUP = 1ull << 36  // k_sweep_narrow_batch: one pass over a narrow (8-byte, num_per <= 64) database for a group of up to 8
 };
 // Run-time tunables (sp_debug_set / environment SPIRAL_<NAME>): read on every launch, so that variants can be A/B
 // measured inside one process on ONE database allocation (HBM placement alone moves the sweep by +-5 %).
@@ -416,7 +417,21 @@ struct SweepBatchDesc {
   // digit-planar copy of the same database (sweep_planar.hpp; sp_db::planar, built on the first group of more than 8 queries):
   // the two-tile pass then runs k_sweep_planar.  nullptr: the PACKED kernels.
   const unsigned char* planar;
+  // narrow form (sweep_narrow_batch.hpp): db is the 8-byte layout [plane][z][j][ii] with 2 <= num_per <= 64 and the pass is
+  // k_sweep_narrow_batch (VALU, no digit table, at most SWEEP_BATCH_MAX members); fold_every = products added to a u64 sum between
+  // two Barrett folds (0 = the switch narrow_batch_fold_every, default 255; the launcher clamps to 1 .. 255)
+  int narrow;
+  int fold_every;
 };
+// does a list on this dense, unsharded 8-byte database share one pass per group (k_sweep_narrow_batch)?  2 <= num_per <= 64;
+// num_per == 1, the 8-byte wide form (num_per >= 128, odd row counts) and row / column shards keep the per-query flow -- the caller
+// checks "unsharded, not PACKED, not sparse"
+bool sweep_narrow_batch_shape_ok(int num_per, int nj);
+// switch narrow_batch_min: the smallest group of a list on such a database that shares one pass (0 = never: every query sweeps
+// alone; negative = this default).  Ships 0: the alternation of profiles/narrow_batch_pass.md names 2, but its per-query flow ran a
+// quarter below the previous build measured in a process of its own, so the gain over that build is not yet established
+constexpr long NARROW_BATCH_MIN_DEFAULT = 0;
+void launch_sweep_narrow_batch(const DevTables& T, const SweepBatchDesc& d, hipStream_t s);   // sweep_planar.hip
 // does this shape have a digit-planar form (whole 64-row blocks, the z-row's query planes in LDS, whole 128-column chunks)?
 bool sweep_planar_shape_ok(int num_per, int nj);
 size_t sweep_planar_bytes(int planes, int num_per, int nj);

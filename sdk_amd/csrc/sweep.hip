@@ -463,6 +463,7 @@ static bool mfma_shape_ok(int num_per, int nj) {
   return tunable("batch_mfma", 1) != 0 && nj > 0 && (nj % 32) == 0 && nj <= 512 && num_per >= 128 && (num_per % 128) == 0;
 }
 bool sweep_batch_wants_mfma(const SweepBatchDesc& d) {
+  if (d.narrow) return false;   // VALU, no digit table
   // below batch_mfma_min queries per pass the VALU kernel is HBM-bound as well
   return mfma_shape_ok(d.num_per, d.nj) && d.batch >= (int)tunable("batch_mfma_min", 4) && d.batch <= SWEEP_GROUP_MAX &&
          (d.batch <= SWEEP_BATCH_MAX || tunable("batch_mfma_tiles", 2) >= 2);
@@ -566,6 +567,10 @@ static void launch_sweep_mfma(const DevTables& T, const SweepBatchDesc& d, hipSt
   launched(PATH_SWEEP_BATCH | PATH_SWEEP_MFMA, "k_sweep_mfma_batch");
 }
 void launch_sweep_batch(const DevTables& T, const SweepBatchDesc& d, hipStream_t s) {
+  if (d.narrow) {   // the 8-byte narrow layout: its own kernel and translation unit (sweep_planar.hip)
+    launch_sweep_narrow_batch(T, d, s);
+    return;
+  }
   if (d.use_mfma && d.rq) {
     launch_sweep_mfma(T, d, s);
     return;

@@ -7,6 +7,7 @@
 #include "device_common.hpp"
 #include "sweep_planar.hpp"
 #include "sweep_mfma_scatter.hpp"
+#include "sweep_narrow_batch.hpp"
 #include "server.hpp"
 
 namespace spiral {
@@ -206,6 +207,35 @@ void launch_sweep_batch_scatter(const DevTables& T, const SweepBatchDesc& d, int
   if (staged) SP_SCATTER(2) else SP_SCATTER(1)
 #undef SP_SCATTER
   launched(PATH_SWEEP_BATCH | PATH_SWEEP_MFMA | PATH_SCATTER_OUT | PATH_SWEEP_BATCH_SCATTER, "k_sweep_mfma_scatter");
+}
+
+// ---- one pass over a narrow database for a group of up to 8 queries (sweep_narrow_batch.hpp) ---------------------------------
+bool sweep_narrow_batch_shape_ok(int num_per, int nj) {
+  return num_per >= 2 && num_per <= 64 && (num_per & (num_per - 1)) == 0 && nj > 0;
+}
+void launch_sweep_narrow_batch(const DevTables& T, const SweepBatchDesc& d0, hipStream_t s) {
+  if (!d0.narrow || d0.batch < 1 || d0.batch > SWEEP_BATCH_MAX || !sweep_narrow_batch_shape_ok(d0.num_per, d0.nj))
+    throw HipError("internal: the narrow batched pass does not take this group");
+  SweepBatchDesc d = d0;
+  for (int b = d.batch; b < SWEEP_BATCH_MAX; b++) {   // dead slots: valid rows to read, never stored
+    d.qv[b] = d.qv[0];
+    d.out[b] = nullptr;
+  }
+  const long fe = d.fold_every > 0 ? d.fold_every : tunable("narrow_batch_fold_every", 255);
+  d.fold_every = (int)std::max(1L, std::min(255L, fe));
+  const dim3 grid((unsigned)((size_t)d.planes * N));
+#define SP_NARROW_BATCH(B_)                                                                                              \
+  {                                                                                                                       \
+    const size_t lds = sweep_narrow_batch_lds(B_);                                                                        \
+    /* more than 64 KiB of dynamic LDS: raised on every launch, on the current device (see launch_sweep_mfma) */          \
+    if (lds > 65536)                                                                                                      \
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep_narrow_batch<B_>),                             \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                               \
+    hipLaunchKernelGGL((k_sweep_narrow_batch<B_>), grid, dim3(256), lds, s, T, d);                                        \
+  }
+  if (d.batch <= 2) SP_NARROW_BATCH(2) else if (d.batch <= 4) SP_NARROW_BATCH(4) else SP_NARROW_BATCH(8)
+#undef SP_NARROW_BATCH
+  launched(PATH_SWEEP_NARROW_GROUP, "k_sweep_narrow_batch");
 }
 
 }  // namespace spiral
