@@ -126,7 +126,8 @@ void* devbuf_alloc(size_t bytes, size_t* guard, long* serial) {
   }
   devbuf_fresh(q, bytes);
   // Fresh device memory is zero-filled and the device drained before the buffer is handed out (alloc_zero, default 1):
-  // no kernel of the library ever reads a word it did not write, but recycled pages hold whatever the previous owner
+  // no kernel of the library ever reads a word it did not write (tests/test_gpu_hardened_buffers.py runs every flow on buffers
+  // filled with 0xA5 / 0xFF and on raw memory between guard regions), but recycled pages hold whatever the previous owner
   // (this process or an earlier tenant of the GPU) left there, and a defect of that kind would otherwise only show on
   // some machines.  Allocation is off the query path (workspaces are allocated whole when they are created).
   if (!gb && tunable("poison_ws", 0) <= 0 && tunable("alloc_zero", 1) != 0) {
@@ -273,7 +274,10 @@ void chacha20_keystream_u64(const uint8_t seed[32], u64* out, size_t count) {
     memcpy(&w, seed + 4 * i, 4);
     init[4 + i] = w;
   }
-  static const bool wide = cpu_has_avx2() && tunable("chacha_scalar", 0) == 0;
+  // (resolved per call, as every switch is: a `static` here froze the first call's answer for the life of the process, and
+  // sp_debug_set("chacha_scalar", 1) after the first keystream selected nothing)
+  static const bool avx2 = cpu_has_avx2();
+  const bool wide = avx2 && tunable("chacha_scalar", 0) == 0;
   u64 ctr = 0;
   size_t done = 0;
   u32 blk[8][16];

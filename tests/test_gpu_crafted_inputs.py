@@ -456,19 +456,25 @@ def _limb_words(rng, n, kind):
 @pytest.mark.parametrize("kinds", [("canonical", "ones"), ("canonical", "full"), ("ones", "canonical"), ("full", "full"), ("ones", "ones"), ("top", "top")],
                          ids=lambda k: "db_%s-q_%s" % k)
 @pytest.mark.parametrize("dim0,num_per", [(64, 4), (512, 32), (16, 64), (300, 128), (64, 256), (512, 1), (700, 2),
-                                          (1024, 2), (1024, 64), (1024, 128), (2048, 4)])
+                                          (1024, 2), (1024, 64), (1024, 128), (2048, 4),
+                                          pytest.param(257, 128, id="odd-257-128"), pytest.param(3, 256, id="odd-3-256")])
 def test_multiply_reg_by_database_any_limbs(sp, oracle_mod, dim0, num_per, kinds):
     """sp_multiply_reg_by_database with limbs >= q up to 2^32 - 1 in `db` and in `v_firstdim`, at every shape of
-    test_multiply_reg_by_database_shapes (k_sweep_narrow, k_sweep_wide, the PACKED kernels).  The reference sums in u128 and is
-    exact for any limbs (server.rs:186-217), the kernels sum up to 256 products in u64: the export reduces both operands' limbs
-    on upload.  `top`: both operands q - 1 in every limb of every row, so that every reduction of a full block of 256 rows sees
+    test_multiply_reg_by_database_shapes (k_sweep_narrow, the PACKED kernels) and at two wide shapes with an odd row count
+    (k_sweep_wide).  The reference sums in u128 and is exact for any limbs (server.rs:186-217), the kernels sum up to 256 products
+    in u64: the export reduces both operands' limbs on upload.  `top`: both operands q - 1 in every limb of every row, so that every reduction of a full block of 256 rows sees
     256 (q - 1)^2 = 0.9995 * 2^64 (reduce64's quotient estimate at its worst: an estimate two short leaves 2q <= r < 3q, which
     one conditional subtraction does not bring below q) and, at 1024 rows, the last block's result is stored as it comes."""
     p, o = sp.Params(FAST), oracle_mod.Params(FAST)
     rng = np.random.default_rng(dim0 * 1000 + num_per)
     db = _limb_words(rng, N * num_per * dim0, kinds[0])
     qv = _limb_words(rng, N * dim0 * 2, kinds[1])
-    assert (sp.multiply_reg_by_database(p, db, qv, dim0, num_per) == o.multiply_reg_by_database(db, qv, dim0, num_per)).all()
+    sp.paths_taken()
+    got = sp.multiply_reg_by_database(p, db, qv, dim0, num_per)
+    taken = sp.paths_taken()
+    assert (got == o.multiply_reg_by_database(db, qv, dim0, num_per)).all()
+    if num_per >= 128:     # an odd row count cannot be PACKED: the 8-byte words and k_sweep_wide
+        assert ("sweep_wide" if dim0 % 2 else "sweep_packed_persist") in taken and len({"sweep_wide", "sweep_packed_persist"} & taken) == 1, taken
 
 
 @pytest.mark.parametrize("num_per_log,dim0_log", [(7, 3), (5, 4)], ids=["packed", "narrow"])

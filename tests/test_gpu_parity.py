@@ -256,12 +256,20 @@ def test_coefficient_expansion_and_regev_to_gsw(sp, oracle_mod):
     assert (sp.regev_to_gsw(p, gpp, v_gsw_inp, o.db_dim_2) == o.regev_to_gsw(v_gsw_inp, v_conv, o.db_dim_2)).all()
 
 
+def wide_sweep_path(dim0, num_per):
+    """the path bit of sp_multiply_reg_by_database at a wide shape: db_can_pack needs an even row count, an odd one keeps the 8-byte
+    words and k_sweep_wide; None for the narrow shapes"""
+    return None if num_per < 128 else "sweep_packed_persist" if dim0 % 2 == 0 else "sweep_wide"
+
+
 @pytest.mark.parametrize("dim0,num_per", [(64, 4), (512, 32), (16, 64), (300, 128), (64, 256), (512, 1), (700, 2),
-                                          (1024, 2), (1024, 64), (1024, 128), (2048, 4)])
+                                          (1024, 2), (1024, 64), (1024, 128), (2048, 4)] +
+                         [pytest.param(d, n, id="odd-%d-%d" % (d, n)) for d, n in ((1, 128), (255, 128), (257, 128), (513, 128), (3, 256))])
 def test_multiply_reg_by_database_shapes(sp, oracle_mod, dim0, num_per):
     """db sweep on random (not NTT-of-plaintext) words incl. ragged dim0 and the >255-row fold path; 1024 rows = nu_1 = 10 of
     CFG_16_100000 (util.rs:21-34: (1024, 64) is its plane shape; (1024, 128) the same depth on the PACKED ring kernel), 2048 rows
-    beyond every shipped configuration."""
+    beyond every shipped configuration.  Odd row counts at num_per >= 128 cannot be PACKED: k_sweep_wide, with one row, one row
+    either side of a full block of 256, two blocks and a row, and two 128-column chunks."""
     p, o = _pair(sp, oracle_mod, FAST)
     rng = np.random.default_rng(dim0 * 1000 + num_per)
     N = 2048
@@ -270,9 +278,31 @@ def test_multiply_reg_by_database_shapes(sp, oracle_mod, dim0, num_per):
     # worst case for the u64 accumulators: all operands maximal
     db[:num_per * dim0] = np.uint64((Q0 - 1) | ((Q1 - 1) << 32))
     qv[:dim0 * 2] = np.uint64((Q0 - 1) | ((Q1 - 1) << 32))
+    sp.paths_taken()
     got = sp.multiply_reg_by_database(p, db, qv, dim0, num_per)
+    taken = sp.paths_taken()
     exp = o.multiply_reg_by_database(db, qv, dim0, num_per)
     assert (got == exp).all()
+    if num_per >= 128:
+        assert wide_sweep_path(dim0, num_per) in taken and len({"sweep_wide", "sweep_packed_persist"} & taken) == 1, taken
+
+
+def test_wide_sweep_all_maximal_closed_form(sp):
+    """k_sweep_wide with (q0 - 1, q1 - 1) in EVERY word of both operands at (513, 128): two full blocks of 256 rows and a one-row tail
+    on every (z, ii).  A block's u64 sum reaches 256 (q0 - 1)^2 + q0 - 1 = 1.84377e19 of 2^64 = 1.84467e19 -- the tightest margin of
+    the sweep family.  The reference is the closed form, with Python integers: every output word is 513 (q - 1)^2 mod q."""
+    dim0, num_per, N = 513, 128, 2048
+    p = sp.Params(FAST)
+    top = np.uint64((Q0 - 1) | ((Q1 - 1) << 32))
+    db = np.full(N * num_per * dim0, top, dtype=np.uint64)
+    qv = np.full(N * dim0 * 2, top, dtype=np.uint64)
+    sp.paths_taken()
+    got = sp.multiply_reg_by_database(p, db, qv, dim0, num_per).reshape(num_per, 2, 2, N)
+    assert "sweep_wide" in sp.paths_taken()
+    assert 256 * (Q0 - 1) ** 2 + Q0 - 1 < 1 << 64
+    for c, q in enumerate((Q0, Q1)):
+        want = dim0 * (q - 1) ** 2 % q
+        assert (got[:, :, c, :] == np.uint64(want)).all(), (c, want, int((got[:, :, c, :] != np.uint64(want)).sum()))
 
 
 def test_fold_pack_encode_stages(sp, oracle_mod):
@@ -629,7 +659,7 @@ def test_db_preprocessing_on_gpu(sp, oracle_mod, cfg, short):
 
 
 @pytest.mark.parametrize("item_size", [1001, 5, 9], ids=["1001B", "5B-spill-3", "9B-spill-3"])
-def test_db_preprocessing_item_spill_across_windows(sp, oracle_mod, monkeypatch, item_size):
+def test_db_preprocessing_item_spill_across_windows(sp, oracle_mod, item_size):
     """db_item_size not a multiple of the chunk count: the chunks of an item cover chunks * bytes_per_chunk bytes, i.e.
     they read into the NEXT item(s) (load_item_from_seek, server.rs:300-309).  The upload windows carry that spill as a
     tail so that this also holds for the last item of a window (here: every second row pair starts a new window); with
@@ -637,11 +667,15 @@ def test_db_preprocessing_item_spill_across_windows(sp, oracle_mod, monkeypatch,
     cfg = dict(FAST, nu_1=4, nu_2=1, db_item_size=item_size)
     o = oracle_mod.Params(cfg)
     p = sp.Params(cfg)
-    monkeypatch.setenv("SPIRAL_DB_LOAD_WINDOW", str(2 * o.num_per * o.db_item_size))
     rng = np.random.default_rng(5)
     blob = rng.integers(1, 256, o.num_items * o.db_item_size, dtype=np.uint8).tobytes()
     exp = o.load_db_from_bytes(blob).reshape(4, 2048, o.num_per, o.dim0)
-    db = sp.Database(p).load_items(blob)
+    # (set with sp_debug_set, as tests/test_gpu_bulk_upsert.py sets it: a value it has left in the process shadows the environment)
+    sp.lib().sp_debug_set(b"db_load_window", C.c_long(2 * o.num_per * o.db_item_size))
+    try:
+        db = sp.Database(p).load_items(blob)
+    finally:
+        sp.lib().sp_debug_set(b"db_load_window", C.c_long(int(os.environ.get("SPIRAL_DB_LOAD_WINDOW", 512 << 20))))
     for pl in range(4):
         for z in (0, 500, 501, 2047):
             for ii in range(o.num_per):
@@ -1507,3 +1541,191 @@ def test_wave_fold_kernel_gadget_widths(sp, oracle_mod, monkeypatch, ci):
         monkeypatch.setenv("SPIRAL_FOLD_SKIP_DEAD_DIGITS", "0")
         p0 = sp.Params(cfg)
         assert sp.process_query(p0, sp.PublicParameters.deserialize(p0, pp), q, sp.Database(p0).load(db)) == expect
+
+
+# ------------------------------------------------------------------------- the 8-byte wide database (db_unpacked, k_sweep_wide)
+UNPACKED_SHAPES = [dict(FAST, nu_1=2, nu_2=7, t_gsw=2, db_item_size=1000), dict(FAST, nu_1=6, nu_2=7, db_item_size=256)]
+UNPACKED_IDS = ["4x128", "64x128"]
+PACKED_PATHS = {"sweep_packed_persist", "sweep_ring", "sweep_batch", "sweep_batch_mfma", "sweep_narrow_group"}
+
+
+def _set(sp, name, value):
+    sp.lib().sp_debug_set(name.encode(), C.c_long(value))
+
+
+def _unpacked_db(sp, p, *shard):
+    """a database handle created under db_unpacked = 1: 8-byte words where the shape would have been PACKED"""
+    _set(sp, "db_unpacked", 1)
+    try:
+        return sp.Database(p, *shard)
+    finally:
+        _set(sp, "db_unpacked", 0)
+
+
+@pytest.mark.parametrize("cfg", UNPACKED_SHAPES, ids=UNPACKED_IDS)
+def test_db_unpacked_words(sp, oracle_mod, cfg):
+    """every writer of a handle made under db_unpacked = 1 leaves the words the reference layout holds: sp_db_load -> sp_db_read_ref,
+    sp_db_load_items == load_db_from_bytes, sp_db_update_item and a three-record sp_db_update_rows body on top, sp_db_fill_synthetic
+    == synth_words; sp_db_prepare_batch builds nothing (the planar copy is the PACKED words') and is no error"""
+    from sdk_amd.spiral import synth_words
+    from test_gpu_bulk_upsert import _body
+    o, p = oracle_mod.Params(cfg), sp.Params(cfg)
+    N, isz = 2048, o.db_item_size
+    rng = np.random.default_rng(o.dim0)
+    n_words = 4 * N * o.num_per * o.dim0
+    words = rng.integers(0, Q0, n_words, dtype=np.uint64) | (rng.integers(0, Q1, n_words, dtype=np.uint64) << np.uint64(32))
+    gdb = _unpacked_db(sp, p).load(words)
+    assert gdb.device_bytes() == n_words * 8                    # (PACKED: 7 bytes per word)
+
+    def same_words(ref, samples=24):
+        ref = ref.reshape(4, N, o.num_per, o.dim0)
+        for pl, z, ii in [(0, 0, 0), (3, N - 1, o.num_per - 1)] + [(int(rng.integers(4)), int(rng.integers(N)), int(rng.integers(o.num_per)))
+                                                                   for _ in range(samples)]:
+            assert (gdb.read_ref(pl, z, ii, 0, o.dim0) == ref[pl, z, ii]).all(), (pl, z, ii)
+    same_words(words)
+    assert gdb.prepare_batch() is False and gdb.batch_copy_bytes() == 0
+    blob = rng.integers(0, 256, o.num_items * isz, dtype=np.uint8)
+    gdb.load_items(blob)
+    same_words(o.load_db_from_bytes(blob.tobytes()))
+    edits = [(1, rng.integers(0, 256, isz - 3, dtype=np.uint8).tobytes())]
+    gdb.update_item(*edits[0])
+    body = [(0, rng.integers(0, 256, isz, dtype=np.uint8).tobytes()), (o.num_items - 1, rng.integers(0, 256, isz - 1, dtype=np.uint8).tobytes()),
+            (o.num_per + 1, b"\x07" * 5)]
+    assert gdb.update_rows(_body(body)) == (3, 4 + isz)
+    for i, d in edits + body:
+        blob[i * isz:(i + 1) * isz] = 0
+        blob[i * isz:i * isz + len(d)] = np.frombuffer(d, dtype=np.uint8)
+    same_words(o.load_db_from_bytes(blob.tobytes()))
+    gdb.fill_synthetic(99)
+    for _ in range(12):
+        pl, z, ii = int(rng.integers(4)), int(rng.integers(N)), int(rng.integers(o.num_per))
+        idx = ((pl * N + z) * o.num_per + ii) * o.dim0 + np.arange(o.dim0, dtype=np.uint64)
+        assert (gdb.read_ref(pl, z, ii, 0, o.dim0) == synth_words(99, idx)).all()
+
+
+@pytest.mark.parametrize("cfg", UNPACKED_SHAPES, ids=UNPACKED_IDS)
+def test_db_unpacked_queries(sp, oracle_mod, cfg):
+    """a single query and a list of 5 on a handle made under db_unpacked = 1: the oracle's bytes through k_sweep_wide and no PACKED
+    kernel.  The list runs with narrow_batch_min = 2 and must stay out of the narrow group pass (sweep_narrow_batch_shape_ok refuses
+    num_per >= 128); once more with sweep_nt_store = 0, the plain-store branch of sweep_store_pair."""
+    from test_gpu_hardened_buffers import _case
+    case = _case(oracle_mod, cfg)
+    qs = case.queries(5)
+    want = case.want(qs)
+    p = sp.Params(cfg)
+    gpps = [sp.PublicParameters.deserialize(p, pp) for _, pp in case.clients]
+    gdb = _unpacked_db(sp, p).load(case.words)
+    for nt_store in (1, 0):
+        _set(sp, "sweep_nt_store", nt_store)
+        _set(sp, "narrow_batch_min", 2)
+        try:
+            sp.paths_taken()
+            one = sp.process_query(p, gpps[qs[0][0]], qs[0][2], gdb)
+            taken = sp.paths_taken()
+            got = sp.process_query_batch(p, [gpps[c] for c, _, _ in qs], [q for _, _, q in qs], gdb)
+            taken_list = sp.paths_taken()
+        finally:
+            _set(sp, "sweep_nt_store", 1)
+            _set(sp, "narrow_batch_min", int(os.environ.get("SPIRAL_NARROW_BATCH_MIN", -1)))
+        assert one == want[0] and got == want, nt_store
+        for t in (taken, taken_list):
+            assert "sweep_wide" in t and not (PACKED_PATHS & t), t
+    if cfg.get("t_gsw", 8) == 8:
+        assert case.clients[0][0].decode_response(one) == case.o.item_to_vec(case.item)
+
+
+def test_db_unpacked_row_sharded_loopback(sp, oracle_mod):
+    """row shards made under db_unpacked = 1 through the library's sharded answer path (G = 2 host threads, loopback transport):
+    k_sweep_wide writes the column-interleaved reduce-scatter layout (the last branch of sweep_store_pair); the oracle's bytes"""
+    from sdk_amd.sharding import LoopbackWorld
+    from test_gpu_hardened_buffers import _case
+    cfg, G = UNPACKED_SHAPES[1], 2
+    case = _case(oracle_mod, cfg)
+    qs = case.queries(2)
+    want = case.want(qs)
+    p = sp.Params(cfg)
+    gpps = [sp.PublicParameters.deserialize(p, pp) for _, pp in case.clients]
+    shards = [_unpacked_db(sp, p, s, G).load(case.words) for s in range(G)]
+    world = LoopbackWorld(G)
+
+    def rank_main(r):
+        sp.lib().sp_set_device(0)
+        sp.paths_taken()
+        return [world.comm(r).process_query(p, gpps[c], q, shards[r]) for c, _, q in qs], sp.paths_taken()
+    res = world.run(rank_main)
+    assert res[0][0] == want
+    for r in range(G):
+        assert {"sweep_wide", "scatter_out", "custom_transport", "expand_pruned"} <= res[r][1] and not (PACKED_PATHS & res[r][1]), res[r][1]
+
+
+# --------------------------------------------------------------------------------- switches that pick device code, one value each
+PACKED_64x128 = UNPACKED_SHAPES[1]
+LDS_STAGED_16x512 = {"n": 2, "nu_1": 4, "nu_2": 9, "p": 256, "q2_bits": 20, "t_gsw": 2, "t_conv": 4, "t_exp_left": 8, "t_exp_right": 56,
+                     "instances": 1, "db_item_size": 8192}
+PIPELINED_32x1024 = dict(LDS_STAGED_16x512, nu_1=5, nu_2=10, t_gsw=4)
+CHUNKS4_32x512 = dict(LDS_STAGED_16x512, nu_1=5, nu_2=9, t_gsw=4, db_item_size=1024)
+CHUNKS4_64x512 = dict(CHUNKS4_32x512, nu_1=6, db_item_size=512)
+
+# (switch, value, shape, what runs: a single query | a list of n, further switches, path names that must / must not be taken)
+_SWITCH_CASES = [
+    ("from_sweep_xcd", 0, PACKED_64x128, [(1, {}, {"from_sweep4"}, {"from_sweep4_xcd_order"})]),
+    ("sweep_persist_wgs", 1, PACKED_64x128, [(1, {"pipe_ring": 0}, {"sweep_packed_persist"}, {"sweep_ring"})]),
+    ("sweep_persist_wgs", 16, PACKED_64x128, [(1, {"pipe_ring": 0}, {"sweep_packed_persist"}, {"sweep_ring"})]),
+    ("fused_min_pairs_cap", 1, PACKED_64x128, [(1, {}, {"fold_fused"}, {"fold_tail_delta"})]),
+    ("no_batch_sweep", 1, PACKED_64x128, [(3, {}, {"sweep_packed_persist"}, {"sweep_batch", "expand_group"})]),
+    ("expand_group_tail", 0, PACKED_64x128, [(8, {}, {"expand_group", "sweep_batch_mfma"}, set())]),
+    ("batch_mfma_tiles", 1, PACKED_64x128, [(16, {}, {"sweep_batch_mfma", "expand_group"}, {"sweep_batch_mfma_two_tiles", "sweep_batch_planar"})]),
+    ("batch_tables_merged", 0, PACKED_64x128, [(16, {}, {"sweep_batch_planar"}, set())]),
+    ("chacha_scalar", 1, PACKED_64x128, [(1, {}, {"sweep_packed_persist"}, set())]),
+    ("batch_qlds_min", 1, LDS_STAGED_16x512, [(11, {}, {"sweep_batch"}, {"sweep_batch_mfma"})]),
+    ("batch_qlds_min", 9, LDS_STAGED_16x512, [(11, {}, {"sweep_batch"}, {"sweep_batch_mfma"})]),
+    ("pipe_wgs", 0, PIPELINED_32x1024, [(1, {}, {"pipelined_fold_overlap", "sweep_ring"}, set()),
+                                       (1, {"pipe_ring": 0}, {"pipelined_fold_overlap", "sweep_packed_persist"}, {"sweep_ring"})]),
+    ("pipe_wgs", 1, PIPELINED_32x1024, [(1, {}, {"pipelined_fold_overlap", "sweep_ring"}, set()),
+                                       (1, {"pipe_ring": 0}, {"pipelined_fold_overlap", "sweep_packed_persist"}, {"sweep_ring"})]),
+    # 512 columns = four 128-column chunks: with cpw below 4 a workgroup owns `cpw` chunks of a z-row and the kernels' chunks / cpw > 1
+    # indexing runs (at every smaller shape the default has one workgroup own all chunks).  The planar copy needs whole 64-row blocks
+    ("batch_mfma_cpw", 1, CHUNKS4_32x512, [(8, {}, {"sweep_batch_mfma"}, {"sweep_batch_mfma_two_tiles"}),
+                                          (16, {"batch_planar": 0}, {"sweep_batch_mfma_two_tiles"}, {"sweep_batch_planar"})]),
+    ("batch_mfma_cpw", 2, CHUNKS4_32x512, [(8, {}, {"sweep_batch_mfma"}, {"sweep_batch_mfma_two_tiles"}),
+                                          (16, {"batch_planar": 0}, {"sweep_batch_mfma_two_tiles"}, {"sweep_batch_planar"})]),
+    ("batch_mfma_cpw", 1, CHUNKS4_64x512, [(16, {}, {"sweep_batch_planar"}, set())]),
+    ("batch_mfma_cpw", 2, CHUNKS4_64x512, [(16, {}, {"sweep_batch_planar"}, set())]),
+]
+
+
+@pytest.mark.parametrize("name,value,cfg,runs", _SWITCH_CASES,
+                         ids=["%s-%d-%dx%d" % (c[0], c[1], 1 << c[2]["nu_1"], 1 << c[2]["nu_2"]) for c in _SWITCH_CASES])
+def test_switches_that_pick_device_code(sp, oracle_mod, name, value, cfg, runs):
+    """Switches that select a kernel, a template instance or an index computation and that no other test names, each at a value it
+    does not have by default: the oracle's bytes, the path names that show which code ran, and the switch restored.  chacha_scalar
+    is the host's keystream (sp_pp_deserialize and the query's seed expansion): the public parameters are exported and compared too."""
+    import contextlib
+    from test_gpu_hardened_buffers import _case, env_switch
+    from test_gpu_narrow_batch import switch
+    case = _case(oracle_mod, cfg)
+    qs = case.queries(max(n for n, _, _, _ in runs))
+    want = case.want(qs)
+
+    def switched(nm, v):
+        # through the environment, so that nothing stays set in the process -- but batch_planar, which other tests set with
+        # sp_debug_set: the environment no longer reaches it
+        return switch(sp, nm, v, default=1) if nm == "batch_planar" else env_switch(nm, v)
+    with switched(name, value):
+        p = sp.Params(cfg)
+        gpps = [sp.PublicParameters.deserialize(p, pp) for _, pp in case.clients]
+        if name == "chacha_scalar":
+            assert (gpps[0].export() == case.o.pp_deserialize_flat(case.clients[0][1])).all()
+        gdb = sp.Database(p).load(case.words)
+        for n, more, must, must_not in runs:
+            with contextlib.ExitStack() as stack:
+                for nm, v in more.items():
+                    stack.enter_context(switched(nm, v))
+                sp.paths_taken()
+                if n == 1:
+                    got = [sp.process_query(p, gpps[qs[0][0]], qs[0][2], gdb)]
+                else:
+                    got = sp.process_query_batch(p, [gpps[c] for c, _, _ in qs[:n]], [q for _, _, q in qs[:n]], gdb)
+                taken = sp.paths_taken()
+            assert got == want[:n], (n, more)
+            assert must <= taken and not (must_not & taken), (n, more, taken)
