@@ -106,6 +106,21 @@ sp_db_t* sp_db_create_columns(const sp_params_t*, int shard, int num_shards);
  * RwLock write guard, bin/server.rs:33,48).  Needs expand_queries and 3 <= t_gsw <= 32. */
 sp_db_t* sp_db_create_sparse(const sp_params_t*);
 size_t sp_db_sparse_items(const sp_db_t*); /* items present */
+/* A PLANAR-RESIDENT database: an unsharded handle whose only resident form is the digit-planar layout that the matrix-core
+ * group pass reads, [plane][z][128-column chunk][wave g][modulus c][64-row block][tile e][digit a][lane][16 bytes] (8 bytes per
+ * word, +14 % against PACKED, and no second copy): every query of every list size reads it -- 1 .. 8 queries per pass with one
+ * query tile, 9 .. 16 with two -- so lists of 9 .. 16 keep their fast pass at sizes where a PACKED database has no room for
+ * the copy of sp_db_prepare_batch.  Choose it where lists dominate; a single query reads 8 instead of 7 bytes per word.
+ * Shapes: dim0 % 64 == 0, dim0 <= 512, num_per % 128 == 0 (else SP_E_ARG); the switches batch_planar and batch_mfma must be on
+ * when it is created (else SP_E_ARG) and are not looked at again: afterwards they, batch_mfma_min and batch_mfma_tiles change
+ * nothing on this handle and never free its words; SP_E_OOM when the words do not fit.  Starts as the empty bucket.
+ * Loaders, upserts, sp_db_read_ref, sp_process_query, sp_query_begin / sweep / finish, sp_process_query_batch,
+ * sp_bench_sweep_batch and sp_server_* work as on a PACKED handle (same bytes); sp_db_prepare_batch builds nothing and reports
+ * 1, sp_db_batch_copy_bytes is 0.  The sp_query_sweep_scatter* family, sp_process_quer{y,ies}_sharded* and sp_bench_sweep[_ex]
+ * refuse it with SP_E_ARG ("planar-resident"). */
+sp_db_t* sp_db_create_planar(const sp_params_t*);
+/* "packed" (7-byte words), "words8" (8-byte words), "sparse" or "planar"; no device call */
+const char* sp_db_format(const sp_db_t*);
 void sp_db_free(sp_db_t*);
 /* Upload (a z-range of) one (instance,trial) plane given in the reference layout [z][ii][j] with
  * the FULL dim0 rows per (z,ii); the shard keeps only its rows.  `words` points at row z0.

@@ -75,6 +75,8 @@ pub mod sys {
         pub fn sp_db_create(p: *const sp_params_t, shard: c_int, num_shards: c_int) -> *mut sp_db_t;
         pub fn sp_db_create_columns(p: *const sp_params_t, shard: c_int, num_shards: c_int) -> *mut sp_db_t;
         pub fn sp_db_create_sparse(p: *const sp_params_t) -> *mut sp_db_t;
+        pub fn sp_db_create_planar(p: *const sp_params_t) -> *mut sp_db_t;
+        pub fn sp_db_format(db: *const sp_db_t) -> *const c_char;
         pub fn sp_db_sparse_items(db: *const sp_db_t) -> usize;
         pub fn sp_db_free(db: *mut sp_db_t);
         pub fn sp_db_load_plane(db: *mut sp_db_t, plane: c_int, z0: c_int, nz: c_int, words: *const u64) -> c_int;
@@ -320,6 +322,19 @@ impl Database {
         let h = unsafe { sys::sp_db_create_sparse(params.0) };
         assert!(!h.is_null(), "sp_db_create_sparse: {}", last_error());
         Database(h)
+    }
+    /// A planar-resident database (`sp_db_create_planar`): the digit-planar layout is its only resident form, read by every
+    /// query of every list size; `Err` when the shape has no such layout, the switches are off or the words do not fit.
+    pub fn planar(params: &Params) -> Result<Self, HipError> {
+        let h = unsafe { sys::sp_db_create_planar(params.0) };
+        if h.is_null() {
+            return Err(HipError { code: sys::SP_E_ARG, message: last_error() });
+        }
+        Ok(Database(h))
+    }
+    /// `"packed"`, `"words8"`, `"sparse"` or `"planar"`.
+    pub fn format(&self) -> String {
+        unsafe { std::ffi::CStr::from_ptr(sys::sp_db_format(self.0)) }.to_string_lossy().into_owned()
     }
     /// Row shard `rank` of `world` (multi-GPU): first-dimension rows [rank*dim0/world, (rank+1)*dim0/world).
     pub fn shard(params: &Params, rank: usize, world: usize) -> Self {

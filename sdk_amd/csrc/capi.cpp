@@ -239,6 +239,79 @@ void upsert_dense(sp_db& d, const std::vector<UpsertRec>& recs) {
   }
 }
 
+// ---- planar-resident databases (sp_db_create_planar): every writer stages words in the handle's upload buffer and stores them to their
+// planar positions from there (planar_resident.hpp); no buffer of the database's size other than the planar words ever exists
+constexpr size_t PLANAR_STAGE_BYTES = (size_t)64 << 20;   // 8-byte words staged per launch, at most (one item or column at least)
+unsigned char* planar_words(sp_db& d) { return reinterpret_cast<unsigned char*>(d.words.p); }
+
+// upserts: `recs` hold each index once.  Per window the existing list encoder (k_db_encode_quads: chunks, log2(p)-bit coefficients,
+// recenter_mod, forward NTT) writes the items' words as an 8-byte database of two rows in the upload buffer -- item r of the window is
+// entry r & 3 of quad r >> 2 -- and k_planar_put_items stores each word's 8 digit bytes.  The device image of a window is
+// [quad table | cell table | item bytes | staged words], each part from a 16-byte boundary (caller holds mu)
+void upsert_planar(sp_db& d, const std::vector<UpsertRec>& recs) {
+  sp_params* h = const_cast<sp_params*>(d.params);
+  const Params& p = h->p;
+  DeviceState& D = h->device_state();
+  const size_t planes = p.planes(), word_bytes = planes * POLY_LEN * 8;   // staged bytes of one item
+  const size_t max_win = (size_t)std::max<long>(1, tunable("db_load_window", (long)512 << 20));
+  const size_t max_items = std::max<size_t>(1, std::min(PLANAR_STAGE_BYTES / word_bytes, UPSERT_MAX_GROUP_PLANES / planes));
+  std::vector<UpsertWindow> wins;   // groups = items here
+  for (size_t i = 0; i < recs.size(); i++) {
+    if (wins.empty() || wins.back().groups >= max_items || wins.back().bytes + recs[i].len > max_win) {
+      wins.emplace_back();
+      wins.back().first = i;
+    }
+    wins.back().groups++;
+    wins.back().bytes += recs[i].len;
+  }
+  auto layout = [&](const UpsertWindow& w, size_t& cells0, size_t& bytes0, size_t& stage0, size_t& np_s) {
+    const size_t quads = (w.groups + 3) / 4;
+    np_s = 2 * quads;
+    cells0 = round16(quads * sizeof(DbQuadRec));
+    bytes0 = cells0 + round16(w.groups * sizeof(PlanarPatchCell));
+    stage0 = bytes0 + round16(w.bytes);
+    return stage0 + 2 * np_s * word_bytes;   // [plane][z][2 rows][np_s columns]
+  };
+  size_t image = 1, cells0, bytes0, stage0, np_s;
+  for (const UpsertWindow& w : wins) image = std::max(image, layout(w, cells0, bytes0, stage0, np_s));
+  d.upload.ensure(image);   // before the first kernel: nothing is allocated between the launches below
+  std::vector<uint8_t> host;
+  for (const UpsertWindow& w : wins) {
+    layout(w, cells0, bytes0, stage0, np_s);
+    host.assign(stage0, 0);
+    DbQuadRec* table = reinterpret_cast<DbQuadRec*>(host.data());
+    PlanarPatchCell* cells = reinterpret_cast<PlanarPatchCell*>(host.data() + cells0);
+    for (size_t q = 0; q < np_s / 2; q++) {
+      table[q].jp = 0;
+      table[q].q = (int)q;
+      for (int ab = 0; ab < 4; ab++) table[q].src[ab] = -1;
+    }
+    size_t off = 0;
+    for (size_t r = 0; r < w.groups; r++) {
+      const UpsertRec& rec = recs[w.first + r];
+      table[r >> 2].src[r & 3] = (long long)off;
+      table[r >> 2].len[r & 3] = (int)rec.len;
+      if (rec.len) memcpy(host.data() + bytes0 + off, rec.data, rec.len);
+      off += rec.len;
+      cells[r] = PlanarPatchCell{(int)(rec.idx / p.num_per()), (int)(rec.idx % p.num_per())};
+    }
+    h2d_sync(d.upload.p, host.data(), stage0);
+    u64* stage = reinterpret_cast<u64*>(d.upload.p + stage0);
+    DbEncodeDesc e = encode_desc(d);
+    e.db = stage;
+    e.packed = 0;
+    e.num_per = (int)np_s;
+    e.nj = 2;
+    e.j0 = 0;
+    e.cm = ColMap{0, 1, (int)np_s};
+    e.win = d.upload.p + bytes0;
+    launch_db_encode_quads(D.T, e, reinterpret_cast<const DbQuadRec*>(d.upload.p), np_s / 2, 0);
+    launch_planar_put_items(planar_words(d), stage, (int)planes, np_s, reinterpret_cast<const PlanarPatchCell*>(d.upload.p + cells0), w.groups,
+                            d.np_local, d.nj, 0);   // same stream, after the encode
+    HIP_CHECK(hipDeviceSynchronize());
+  }
+}
+
 // `n` checked records in call order -> what sp_db_update_item on each in turn would leave: a later record for an index wins
 // (deduplicated here, before anything is launched; the survivors keep the order of first appearance, which is the order sequential
 // calls hand out a sparse bucket's slots in)
@@ -258,6 +331,8 @@ void upsert_many(sp_db& d, const UpsertRec* in, size_t n) {
   std::lock_guard<std::mutex> lk(d.mu);
   if (d.sparse)
     upsert_sparse(d, recs);
+  else if (d.planar_resident)
+    upsert_planar(d, recs);
   else
     upsert_dense(d, recs);
 }
@@ -285,6 +360,12 @@ SweepBatchDesc spiral::group_pass(const sp_db& db, sp_query_t* const* qs, int B,
     d.qv[i] = qs[i]->ws->qv.p;
     d.out[i] = qs[i]->ws->sweep_out.p;
   }
+  if (db.planar_resident) {   // the resident words are the planar operands: one or two tiles' tables, nothing to pin
+    W0.batch_rq.ensure(sweep_batch_rq_words(d.nj, sweep_batch_tiles(d.batch)));
+    d.rq = W0.batch_rq.p;
+    d.planar = reinterpret_cast<const unsigned char*>(db.words.p);
+    return d;
+  }
   d.narrow = !db.packed;   // the 8-byte layout: callers come here only where sweep_narrow_batch_shape_ok holds
   if (sweep_batch_wants_mfma(d)) {
     W0.batch_rq.ensure(sweep_batch_rq_words(d.nj, sweep_batch_tiles(d.batch)));
@@ -293,6 +374,19 @@ SweepBatchDesc spiral::group_pass(const sp_db& db, sp_query_t* const* qs, int B,
   }
   d.planar = pin ? reinterpret_cast<const unsigned char*>(pin->p) : nullptr;
   return d;
+}
+void spiral::group_pass_launch(const sp_db& db, const DevTables& T, SweepBatchDesc& d, hipStream_t s) {
+  if (db.planar_resident) {
+    sweep_planar_resident_prepare(T, d, s);
+    launch_sweep_planar_resident(T, d, s);
+    return;
+  }
+  sweep_batch_prepare(T, d, s);
+  launch_sweep_batch(T, d, s);
+}
+void spiral::refuse_planar_resident(const sp_db_t* db, const char* what) {
+  if (db && db->planar_resident)
+    throw ArgError(std::string(what) + " does not take a planar-resident database (sp_db_create_planar): its words are read by the group pass only");
 }
 Workspace& spiral::group_pass_stream(sp_query_t* const* qs, int B) {
   Workspace& W0 = *qs[0]->ws;
@@ -479,6 +573,7 @@ struct ScatterLayout {
 
 void spiral::scatter_group_check(sp_query_t* const* qs, int batch, const sp_db_t* db, int G) {
   need(qs && db, "null argument");
+  refuse_planar_resident(db, "sp_query_sweep_scatter_group");
   need(batch >= 1 && batch <= SWEEP_BATCH_MAX, "sp_query_sweep_scatter_group: 1 .. 8 queries per pass");
   need_row_shard(db);
   need_shard_count(db->params->p, G, db);
@@ -696,6 +791,37 @@ sp_db_t* sp_db_create_sparse(const sp_params_t* h) {
     return d;
   });
 }
+// A database whose only resident form is the digit-planar layout (sweep_planar.hpp): one copy of 8 bytes per word that every query
+// of every list size reads.  Unsharded; the empty database (all-zero polynomials) is every byte 0x80, the offset digit of 0.
+sp_db_t* sp_db_create_planar(const sp_params_t* h) {
+  return guarded_handle([&] {
+    need(h != nullptr, "params is null");
+    const Params& p = h->p;
+    if (!planar_resident_shape_ok((int)std::min<size_t>(p.num_per(), 1u << 30), (int)std::min<size_t>(p.dim0(), 1u << 30)))
+      throw ArgError("sp_db_create_planar: the digit-planar layout needs dim0 % 64 == 0, dim0 <= 512 and num_per % 128 == 0 (dim0 = " +
+                     std::to_string(p.dim0()) + ", num_per = " + std::to_string(p.num_per()) + ")");
+    need(tunable("batch_planar", 1) != 0 && tunable("batch_mfma", 1) != 0,
+         "sp_db_create_planar: the switches batch_planar and batch_mfma must be on when a planar-resident database is created");
+    auto d = std::make_unique<sp_db>();
+    d->params = h;
+    HIP_CHECK(hipGetDevice(&d->device));
+    d->planar_resident = true;
+    d->planar_state = -1;   // no copy beside the words, ever
+    d->packed = 0;
+    d->nj = (int)p.dim0();
+    d->np_local = (int)p.num_per();
+    const size_t bytes = sweep_planar_bytes((int)p.planes(), d->np_local, d->nj);   // a multiple of 8
+    d->words.alloc_streaming(bytes / 8, tunable("db_contiguous", 0) != 0);   // throws OomError
+    HIP_CHECK(hipMemset(d->words.p, 0x80, bytes));
+    HIP_CHECK(hipDeviceSynchronize());
+    const_cast<sp_params*>(h)->device_state();
+    return d;
+  });
+}
+const char* sp_db_format(const sp_db_t* d) {
+  if (!d) return "";
+  return d->sparse ? "sparse" : d->planar_resident ? "planar" : d->packed ? "packed" : "words8";
+}
 size_t sp_db_sparse_items(const sp_db_t* d) {
   if (!d || !d->sparse) return 0;
   std::lock_guard<std::mutex> lk(const_cast<sp_db*>(d)->mu);
@@ -728,8 +854,11 @@ int sp_db_load_plane(sp_db_t* d, int plane, int z0, int nz, const uint64_t* word
     for (int z = 0; z < nz; z += zs) {
       const int cnt = std::min(zs, nz - z);
       h2d_sync(d->upload.p, words + (size_t)z * row_words, (size_t)cnt * row_words * 8);
-      launch_db_relayout(d->words.p, plane, stage, z0 + z, cnt, d->np_local, (int)p.dim0(), d->j0, d->nj,
-                         d->packed, d->colmap(), 0);
+      if (d->planar_resident)   // the window of z-rows straight to planar entries
+        launch_planar_from_ref(planar_words(*d), stage, plane, z0 + z, cnt, d->np_local, d->nj, 0);
+      else
+        launch_db_relayout(d->words.p, plane, stage, z0 + z, cnt, d->np_local, (int)p.dim0(), d->j0, d->nj,
+                           d->packed, d->colmap(), 0);
       HIP_CHECK(hipDeviceSynchronize());
     }
   });
@@ -767,6 +896,42 @@ int sp_db_load_items(sp_db_t* d, const uint8_t* file, size_t file_len) {
     need(logp >= 1 && logp <= 28, "plaintext modulus out of range");
     // windows of whole row pairs: the rows' items are contiguous in the file
     const size_t row_bytes = p.num_per() * p.db_item_size;
+    if (d->planar_resident) {
+      // windows of one 16-row group (the rows of one planar entry): its raw items, then per span of `ncols` columns the existing
+      // encoder writes the span as an 8-byte database of 16 rows x ncols columns behind them in the upload buffer and
+      // k_planar_from_stage stores whole entries.  The tail is that of the PACKED loader below.
+      const size_t tail = std::max(bpc, chunks * bpc - p.db_item_size);
+      const size_t raw = round16(16 * row_bytes + tail);
+      int ncols = 128;   // divides num_per
+      while (ncols > 2 && chunks * POLY_LEN * 16 * (size_t)ncols * 8 > PLANAR_STAGE_BYTES) ncols /= 2;
+      d->upload.ensure(raw + chunks * POLY_LEN * 16 * (size_t)ncols * 8);
+      u64* stage = reinterpret_cast<u64*>(d->upload.p + raw);
+      for (int jg = 0; jg < d->nj / 16; jg++) {
+        const size_t item0 = (size_t)16 * jg * p.num_per();
+        const size_t off = item0 * p.db_item_size;
+        const size_t have = off < file_len ? std::min(16 * row_bytes + tail, file_len - off) : 0;
+        if (have) h2d_sync(d->upload.p, file + off, have);
+        for (int ii0 = 0; ii0 < d->np_local; ii0 += ncols) {
+          DbEncodeDesc e = encode_desc(*d);
+          e.db = stage;
+          e.packed = 0;
+          e.num_per = ncols;
+          e.cm = ColMap{ii0, 1, d->np_local};
+          e.j0 = 16 * jg;
+          e.nj = 16;
+          e.win = d->upload.p;
+          e.win_item0 = item0;
+          e.win_bytes = have;
+          e.file_len = file_len;
+          e.jp0 = 0;
+          e.njp = 8;
+          launch_db_encode(D.T, e, 0);
+          launch_planar_from_stage(planar_words(*d), stage, (int)chunks, jg, ii0, ncols, d->np_local, d->nj, 0);
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+      }
+      return;
+    }
     const int npairs_total = (d->nj + 1) / 2;
     const size_t max_win = (size_t)std::max<long>(1, tunable("db_load_window", (long)512 << 20));  // bytes of raw items per upload
     const int pairs_per_win = (int)std::max<size_t>(1, std::min<size_t>((size_t)npairs_total, max_win / (2 * row_bytes)));
@@ -831,6 +996,11 @@ int sp_db_update_item(sp_db_t* d, size_t item_idx, const uint8_t* data, size_t l
                                 (u32)p.pt_modulus, d->polys.p + slot * poly_words, (int)planes, 0);
       HIP_CHECK(hipDeviceSynchronize());
       if (new_key) d->index_dirty = true;   // an overwrite (the reference's upsert of an existing key) leaves the index alone
+      return;
+    }
+    if (d->planar_resident) {   // a list of one: the item's 8 digit bytes per (plane, z)
+      const UpsertRec one{item_idx, data, len};
+      upsert_many(*d, &one, 1);
       return;
     }
     const size_t j = item_idx / p.num_per(), ii = item_idx % p.num_per();
@@ -918,7 +1088,10 @@ int sp_db_fill_synthetic(sp_db_t* d, uint64_t seed) {
     check_device(d->device);
     sp_db::WriteScope write(*d);
     const Params& p = d->params->p;
-    launch_db_synth(d->words.p, seed, (int)p.planes(), d->np_local, (int)p.dim0(), d->j0, d->nj, d->packed, d->colmap(), 0);
+    if (d->planar_resident)
+      launch_planar_synth(planar_words(*d), seed, (int)p.planes(), d->np_local, d->nj, 0);
+    else
+      launch_db_synth(d->words.p, seed, (int)p.planes(), d->np_local, (int)p.dim0(), d->j0, d->nj, d->packed, d->colmap(), 0);
     HIP_CHECK(hipDeviceSynchronize());
   });
 }
@@ -930,7 +1103,8 @@ int sp_db_prepare_batch(sp_db_t* d, int* built) {
   return guarded([&] {
     need(d != nullptr, "null db");
     check_device(d->device);
-    const bool c = !d->sparse && d->ensure_planar(nullptr);
+    // (a planar-resident database is what the lists read already: nothing to build, nothing allocated)
+    const bool c = d->planar_resident || (!d->sparse && d->ensure_planar(nullptr));
     if (built) *built = c;
   });
 }
@@ -946,7 +1120,10 @@ int sp_db_read_ref(const sp_db_t* d, int plane, int z, int ii, int j0, int count
     need(ii % d->col_G == d->col_g, "column is held by another shard");
     check_device(d->device);
     DevBuf<u64> tmp((size_t)std::max(count, 1));
-    launch_db_read(tmp.p, d->words.p, plane, z, ii / d->col_G, j0, count, d->np_local, d->nj, d->packed, 0);
+    if (d->planar_resident)
+      launch_planar_read(tmp.p, reinterpret_cast<const unsigned char*>(d->words.p), plane, z, ii, j0, count, d->np_local, d->nj, 0);
+    else
+      launch_db_read(tmp.p, d->words.p, plane, z, ii / d->col_G, j0, count, d->np_local, d->nj, d->packed, 0);
     HIP_CHECK(hipMemcpy(out, tmp.p, (size_t)count * 8, hipMemcpyDeviceToHost));
   });
 }
@@ -1072,6 +1249,13 @@ int sp_query_sweep(sp_query_t* q, const sp_db_t* db) {
       // the snapshot the expansion was pruned with (items written after sp_query_begin are not part of this query)
       run_sweep_sparse(W, *db, q->sparse_index->col_ptr.p, q->sparse_index->col_rows.p, q->sparse_index->col_slots.p);
       W.zero_shortcuts = true;
+    } else if (db->planar_resident) {
+      // a group of one: the one-tile pass on the query's own stream (the VALU and ring kernels never see this handle)
+      W.ensure_sweep();
+      sp_query_t* one[1] = {q};
+      PlanarPin none;
+      SweepBatchDesc d = group_pass(*db, one, 1, false, none);
+      group_pass_launch(*db, W.D->T, d, W.stream);
     } else if (sweep_is_pipelined(q->params->p, *db))
       run_sweep_pipelined(W, *db);
     else
@@ -1084,6 +1268,7 @@ int sp_query_sweep(sp_query_t* q, const sp_db_t* db) {
 int sp_query_sweep_scatter(sp_query_t* q, const sp_db_t* db, int G) {
   return guarded([&] {
     need(q && db, "null argument");
+    refuse_planar_resident(db, "sp_query_sweep_scatter");
     need(q->state == 1, "sp_query_sweep_scatter: query not in 'begun' state");
     need(db->params == q->params, "db was created for different params");
     need_rows_of(q, db);
@@ -1101,6 +1286,7 @@ int sp_query_sweep_scatter(sp_query_t* q, const sp_db_t* db, int G) {
 int sp_query_sweep_scatter_plane(sp_query_t* q, const sp_db_t* db, int G, int plane) {
   return guarded([&] {
     need(q && db, "null argument");
+    refuse_planar_resident(db, "sp_query_sweep_scatter_plane");
     need(db->params == q->params, "db was created for different params");
     need_rows_of(q, db);
     const Params& p = q->params->p;

@@ -153,7 +153,8 @@ struct GroupedFlow : GroupsInFlight {
   // a list of exactly 9 .. 16 queries is one group; longer lists are cut into groups of group_max (a last group of <= 8
   // takes the one-tile pass)
   void decide_group_max() {
-    const int shape_max = sweep_batch_group_max(a.db->np_local, a.db->nj);
+    // (a planar-resident database: both tiles whatever the switches say now -- they were read when it was created)
+    const int shape_max = a.db->planar_resident ? planar_resident_group_max(a.db->nj) : sweep_batch_group_max(a.db->np_local, a.db->nj);
     group_max = (int)tunable("batch_group", 0);
     if (group_max <= 0) group_max = shape_max;
     group_max = std::max(1, std::min(shape_max, group_max));
@@ -209,10 +210,9 @@ struct GroupedFlow : GroupsInFlight {
     Workspace& W0 = group_pass_stream(qs, B);
     if (prev_pass) HIP_CHECK(hipStreamWaitEvent(W0.stream, prev_pass, 0));
     SweepBatchDesc d = group_pass(*a.db, qs, B, use_planar, qs[0]->planar);
-    sweep_batch_prepare(W0.D->T, d, W0.stream);
     // (a per-plane form of the pass with every query folding plane p beside the pass of plane p + 1 was measured in rounds
     // 2 and 3 and is slower: the pass leaves no registers for a fold workgroup; profiles/r02_fold_batch_experiments.md)
-    launch_sweep_batch(W0.D->T, d, W0.stream);
+    group_pass_launch(*a.db, W0.D->T, d, W0.stream);
     group_pass_done(qs, 0);
     prev_pass = W0.ev[2];
     stamp("pass enqueued");
@@ -279,7 +279,8 @@ struct GroupedFlow : GroupsInFlight {
     int rc = guarded([&] { run_groups(); });
     // Out of memory (the hipMemGetInfo estimates above are rough): give up, one after the other, what only makes the call faster, and
     // answer the REST of the list each time -- responses already copied out stay.
-    for (int step = narrow_min > 0 ? 2 : 1; rc == SP_E_OOM && step <= 3; step++) {   // (a narrow database has no planar copy)
+    // (a narrow database has no planar copy; a planar-resident one has nothing but its planar words, which are not given up)
+    for (int step = narrow_min > 0 || a.db->planar_resident ? 2 : 1; rc == SP_E_OOM && step <= 3; step++) {
       abandon();
       (void)hipGetLastError();
       start = (int)drained;
@@ -425,6 +426,7 @@ extern "C" int sp_process_query_batch(const sp_params_t* h, const sp_pp_t* const
   const BatchArgs a{h, pps, queries, query_lens, batch, db, out, out_stride, out_len, std::chrono::steady_clock::now()};
   const bool batched = db->packed && db->num_shards == 1 && db->col_G == 1 && !tunable("no_batch_sweep", 0);
   if (db->sparse) return answer_sparse(a);
+  if (db->planar_resident) return answer_in_groups(a);   // lists of any length: groups of up to 16, whatever the switches say now
   if (batched) return answer_in_groups(a);
   const bool narrow = !db->packed && db->num_shards == 1 && db->col_G == 1 && !tunable("no_batch_sweep", 0);
   return narrow ? answer_narrow(a) : answer_in_flight(a);

@@ -149,6 +149,12 @@ using PlanarPin = std::shared_ptr<const DevBuf<u64>>;
 // reused) and, for two query tiles, the digit-planar copy -- pinned in `pin`, which the caller holds until that stream has been
 // synchronised.
 SweepBatchDesc group_pass(const sp_db& db, sp_query_t* const* qs, int B, bool use_planar, PlanarPin& pin);
+// ... and the group's query tables and pass enqueued on `s`: the planar-resident kernels for such a handle (no switch is asked), else
+// sweep_batch_prepare + launch_sweep_batch
+void group_pass_launch(const sp_db& db, const DevTables& T, SweepBatchDesc& d, hipStream_t s);
+// throws ArgError naming the format when `db` is planar-resident: the entry points that sweep per plane, in the scatter layout or on
+// shards
+void refuse_planar_resident(const sp_db_t* db, const char* what);
 // The order around it.  The pass waits for every member's expansion: ev[1], recorded on the member's stream (the operand of the
 // pass, qv, is written on that stream also when the odd subtree was split off); returns the first member's workspace ...
 Workspace& group_pass_stream(sp_query_t* const* qs, int B);

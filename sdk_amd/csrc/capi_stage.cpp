@@ -77,6 +77,7 @@ int sp_bench_sweep(sp_query_t* q, const sp_db_t* db, int iters, float* ms_per_la
 int sp_bench_sweep_ex(sp_query_t* q, const sp_db_t* db, int iters, int per_plane_launches, float* ms_per_launch) {
   return guarded([&] {
     need(q && db && ms_per_launch && iters > 0, "bad argument");
+    refuse_planar_resident(db, "sp_bench_sweep");
     need(q->state >= 1, "query not begun");
     check_device(db->device);
     Workspace& W = *q->ws;
@@ -109,11 +110,12 @@ int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, in
       *ms_per_pass = timed_reps(s, iters, [&] { sparse_group_pass(*db, qs, batch, s); });
       return;
     }
-    need(qs && db && ms_per_pass && iters > 0 && batch >= 1 && batch <= sweep_batch_group_max(db ? db->np_local : 0, db ? db->nj : 0), "bad argument");
+    const int group_max = !db ? 0 : db->planar_resident ? planar_resident_group_max(db->nj) : sweep_batch_group_max(db->np_local, db->nj);
+    need(qs && db && ms_per_pass && iters > 0 && batch >= 1 && batch <= group_max, "bad argument");
     // ... or an unsharded narrow one (8-byte words, 2 <= num_per <= 64) for 2 .. 8 queries: the group's one pass, k_sweep_narrow_batch
     // (a single query is never a group there: it is refused as on every other 8-byte database)
     const bool narrow = !db->packed && db->num_shards == 1 && db->col_G == 1 && batch >= 2 && sweep_narrow_batch_shape_ok(db->np_local, db->nj);
-    need(narrow || (db->packed && db->num_shards == 1 && db->col_G == 1), "the batched pass needs an unsharded PACKED database");
+    need(narrow || db->planar_resident || (db->packed && db->num_shards == 1 && db->col_G == 1), "the batched pass needs an unsharded PACKED database");
     check_device(db->device);
     for (int i = 0; i < batch; i++) {
       need(qs[i] && qs[i]->state >= 1, "query not begun");
@@ -127,10 +129,7 @@ int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, in
     }
     PlanarPin pin;   // held for the whole call: on every path out the pass's stream is synchronised (timed_reps) before it is released
     SweepBatchDesc d = group_pass(*db, qs, batch, true, pin);
-    *ms_per_pass = timed_reps(W0.stream, iters, [&] {
-      sweep_batch_prepare(W0.D->T, d, W0.stream);
-      launch_sweep_batch(W0.D->T, d, W0.stream);
-    });
+    *ms_per_pass = timed_reps(W0.stream, iters, [&] { group_pass_launch(*db, W0.D->T, d, W0.stream); });
   });
 }
 

@@ -49,6 +49,12 @@ void hip_ok(hipError_t e, const char* what) {
 void nccl_ok(ncclResult_t r, const char* what) {
   if (r != ncclSuccess) throw Fail{SP_E_HIP, std::string(what) + ": " + ncclGetErrorString(r)};
 }
+// a planar-resident database (sp_db_create_planar) is never a shard: the sharded flows sweep PACKED or 8-byte words per plane
+bool refuse_planar(const sp_db_t* shard, const char* what) {
+  if (std::strcmp(sp_db_format(shard), "planar") != 0) return false;
+  sp_set_last_error_((std::string(what) + " does not take a planar-resident database (sp_db_create_planar): sharded flows need PACKED or 8-byte shards").c_str());
+  return true;
+}
 void sp_ok(int rc, const char* what) {
   if (rc != SP_OK) throw Fail{rc, std::string(what) + ": " + sp_last_error()};
 }
@@ -361,6 +367,7 @@ int sp_process_query_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t* 
     sp_set_last_error_("null argument");
     return SP_E_ARG;
   }
+  if (refuse_planar(shard, "sp_process_query_sharded")) return SP_E_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   ShardedRun r;
   int rc = guarded_comm([&] {
@@ -427,6 +434,7 @@ int sp_process_queries_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t
     sp_set_last_error_("null argument");
     return SP_E_ARG;
   }
+  if (refuse_planar(shard, "sp_process_queries_sharded")) return SP_E_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   return queries_sharded_locked(c, h, pps, queries, query_lens, n, shard, out, out_stride, out_len);
 }
@@ -448,6 +456,7 @@ int sp_process_queries_sharded_batched(sp_comm_t* c, const sp_params_t* h, const
     sp_set_last_error_("null argument");
     return SP_E_ARG;
   }
+  if (refuse_planar(shard, "sp_process_queries_sharded_batched")) return SP_E_ARG;
   if (group < 0 || group > 8) {
     sp_set_last_error_("group must be 0 (the library's choice) or 1 .. 8");
     return SP_E_ARG;

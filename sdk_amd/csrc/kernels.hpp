@@ -452,6 +452,28 @@ struct PlanarPatchCell {
 void launch_planar_patch_items(unsigned char* planar, const u64* packed, int planes, int num_per, int nj, const PlanarPatchCell* cells,
                                size_t n_cells, hipStream_t s);
 void launch_sweep_planar(const DevTables& T, const SweepBatchDesc& d, hipStream_t s);   // sweep_planar.hip
+// ---- planar-resident databases (sp_db_create_planar): the digit-planar layout is the handle's ONLY resident form (planar_resident.hpp,
+// launched from sweep_planar.hip).  _shape_ok is sweep_planar_shape_ok's rule without the switches (they are read when the handle is
+// created and never again); _group_max = 16 where the device offers both tiles' z-rows of LDS to one workgroup, else 8.
+bool planar_resident_shape_ok(int num_per, int nj);
+int planar_resident_group_max(int nj);
+// writers, all from words staged in the handle's upload buffer: reference words src[nz][num_per][nj] of z-rows z0 .. of `plane`;
+// sp_synth_word(seed, reference index); the 16-row group jg of columns ii0 .. ii0 + ncols - 1 from the 8-byte words
+// stage[plane][z][16][ncols] k_db_encode wrote; `n_items` single items from the 8-byte words k_db_encode_quads wrote as a database of
+// two rows and np_s columns (item r = entry r & 3 of quad r >> 2; cells[r] = its local row and column, an item listed once)
+void launch_planar_from_ref(unsigned char* planar, const u64* src, int plane, int z0, int nz, int num_per, int nj, hipStream_t s);
+void launch_planar_synth(unsigned char* planar, u64 seed, int planes, int num_per, int nj, hipStream_t s);
+void launch_planar_from_stage(unsigned char* planar, const u64* stage, int planes, int jg, int ii0, int ncols, int num_per, int nj,
+                              hipStream_t s);
+void launch_planar_put_items(unsigned char* planar, const u64* stage, int planes, size_t np_s, const PlanarPatchCell* cells, size_t n_items,
+                             int num_per, int nj, hipStream_t s);
+// canonical words (plane, z, ii, rows jl0 .. + count) gathered back from their digit bytes into out[count] (device)
+void launch_planar_read(u64* out, const unsigned char* planar, int plane, int z, int ii, int jl0, int count, int num_per, int nj,
+                        hipStream_t s);
+// a group of 1 .. 16 queries over such a database (d.planar = its words, d.rq = sweep_batch_rq_words(nj, tiles) words of scratch): the
+// query tables, then the pass -- k_sweep_planar with one query tile for 1 .. 8 queries, launch_sweep_planar for 9 .. 16
+void sweep_planar_resident_prepare(const DevTables& T, SweepBatchDesc& d, hipStream_t s);
+void launch_sweep_planar_resident(const DevTables& T, const SweepBatchDesc& d, hipStream_t s);
 // does this shape / group size run on the matrix cores (switch batch_mfma, default on from batch_mfma_min = 4 queries)?
 // Groups of more than SWEEP_BATCH_MAX queries exist only there.
 bool sweep_batch_wants_mfma(const SweepBatchDesc& d);

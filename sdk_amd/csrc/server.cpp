@@ -1251,6 +1251,8 @@ void join_right(Workspace& W) {
 }
 
 void run_sweep(Workspace& W, const sp_db& db) {
+  // (the last line of defence: the entry points that would come here refuse such a handle by name before anything is enqueued)
+  if (db.planar_resident) throw ArgError("the single-query sweep kernels do not read a planar-resident database (sp_db_create_planar)");
   const Params& p = *W.P;
   W.ensure_sweep();
   SweepDesc d{db.words.p, W.qv.p, W.sweep_out.p, (int)p.planes(), db.np_local, (int)p.dim0(), db.j0, db.nj, db.packed, W.out_G};
@@ -1349,6 +1351,8 @@ bool sweep_is_pipelined(const Params& p, const sp_db& db) {
 }
 
 void launch_plane_sweep(Workspace& W, const sp_db& db, size_t pl) {
+  // (the last line of defence: the entry points that would come here refuse such a handle by name before anything is enqueued)
+  if (db.planar_resident) throw ArgError("the single-query sweep kernels do not read a planar-resident database (sp_db_create_planar)");
   const Params& p = *W.P;
   const size_t np_ = (size_t)db.np_local;
   const size_t plane_db_words = db_bytes(1, db.np_local, db.nj, db.packed) / 8;  // N*nj*np*{7,8} is a multiple of 8

@@ -221,6 +221,12 @@ struct sp_db {
     if (planar_state != -1) planar_state = 0;
     planar.reset();
   }
+  // sp_db_create_planar: `words` IS the digit-planar layout (sweep_planar.hpp; planar_resident.hpp writes it), 8 bytes per word and
+  // the handle's only resident form: packed = 0, planar_state = -1 and `planar` stays empty for the handle's life, so ensure_planar,
+  // drop_planar, WriteScope and the out-of-memory ladder of the list flow find nothing to build or to give back.  Every query, alone
+  // or in a list, goes through the group flow (k_sweep_planar with one or two query tiles); the per-plane sweeps, the scatter forms
+  // and shards do not exist for it.  Decided from the switches when the handle is created, never looked at again.
+  bool planar_resident = false;
   std::mutex mu;
   // a bulk write of `words`: holds `mu` and, on every path out (after the last write has completed), drops the planar copy
   // before unlocking (a build between an early invalidation and the end of the write would stay valid and stale)

@@ -2,15 +2,21 @@
 // builds the copy.  Its own translation unit: sweep.hip's kernels -- the judged single-query sweep among them -- compile to the same
 // machine code whether or not this file changes (bench.py replays the sweep's PMC traffic record only into a library whose
 // kernel has the recorded signature, sdk_amd/kernel_signature.py).
-// (sweep_mfma.hpp's one-tile table kernels come along with the shared digit helpers and are not launched from here)
+// (of sweep_mfma.hpp's one-tile table kernels, which come along with the shared digit helpers, only k_query_offset_terms is launched
+// from here: by the one-tile pass over a planar-resident database, at the end of this file)
 #pragma clang diagnostic ignored "-Wunused-function"
 #include "device_common.hpp"
 #include "sweep_planar.hpp"
 #include "sweep_mfma_scatter.hpp"
 #include "sweep_narrow_batch.hpp"
+#include "planar_resident.hpp"
 #include "server.hpp"
 
 namespace spiral {
+
+// second launch bound of the one-tile pass over a planar-resident database: waves per SIMD the registers have to allow (see
+// launch_sweep_planar_resident)
+constexpr int PLANAR1_MINWG = 2;
 
 void launch_query_digits_planar(const QueryDigitsDesc& q, size_t entries, hipStream_t s) {
   hipLaunchKernelGGL(k_query_digits_planar, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, q);
@@ -236,6 +242,122 @@ void launch_sweep_narrow_batch(const DevTables& T, const SweepBatchDesc& d0, hip
   if (d.batch <= 2) SP_NARROW_BATCH(2) else if (d.batch <= 4) SP_NARROW_BATCH(4) else SP_NARROW_BATCH(8)
 #undef SP_NARROW_BATCH
   launched(PATH_SWEEP_NARROW_GROUP, "k_sweep_narrow_batch");
+}
+
+// ---- planar-resident databases (sp_db_create_planar; planar_resident.hpp) ----------------------------------------------------
+// the shape rule alone: what was decided from the switches when the handle was created holds for its life
+bool planar_resident_shape_ok(int num_per, int nj) { return nj > 0 && (nj % 64) == 0 && nj <= 512 && num_per >= 128 && (num_per % 128) == 0; }
+// groups of 9 .. 16 need both tiles' z-rows of query planes in one workgroup's LDS (nj * 256 bytes)
+int planar_resident_group_max(int nj) {
+  int dev = 0, lds_optin = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds_optin, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return SWEEP_BATCH_MAX;
+  }
+  return (size_t)lds_optin >= (size_t)nj * 256 ? SWEEP_GROUP_MAX : SWEEP_BATCH_MAX;
+}
+void launch_planar_from_ref(unsigned char* planar, const u64* src, int plane, int z0, int nz, int num_per, int nj, hipStream_t s) {
+  if (nz <= 0) return;
+  const size_t threads = (size_t)nz * (size_t)num_per * (size_t)(nj >> 4);
+  hipLaunchKernelGGL(k_planar_from_ref, dim3((unsigned)std::min<size_t>((threads + 255) / 256, 256 * 64)), dim3(256), 0, s, planar, src,
+                     (size_t)plane * N + (size_t)z0, nz, num_per, nj);
+  launched(0, "k_planar_from_ref");
+}
+void launch_planar_synth(unsigned char* planar, u64 seed, int planes, int num_per, int nj, hipStream_t s) {
+  hipLaunchKernelGGL(k_planar_synth, dim3(256 * 64), dim3(256), 0, s, planar, seed, (size_t)planes * N, num_per, nj);
+  launched(0, "k_planar_synth");
+}
+void launch_planar_from_stage(unsigned char* planar, const u64* stage, int planes, int jg, int ii0, int ncols, int num_per, int nj,
+                              hipStream_t s) {
+  const size_t threads = (size_t)planes * N * (size_t)ncols;
+  hipLaunchKernelGGL(k_planar_from_stage, dim3((unsigned)std::min<size_t>((threads + 255) / 256, 256 * 64)), dim3(256), 0, s, planar, stage,
+                     (size_t)planes * N, jg, ii0, ncols, num_per, nj);
+  launched(0, "k_planar_from_stage");
+}
+void launch_planar_put_items(unsigned char* planar, const u64* stage, int planes, size_t np_s, const PlanarPatchCell* cells, size_t n_items,
+                             int num_per, int nj, hipStream_t s) {
+  if (n_items == 0) return;
+  const size_t zps = (size_t)planes * N;   // (n_items * planes * N / 256 blocks: the caller's windows keep n_items * planes <= 2^23)
+  hipLaunchKernelGGL(k_planar_put_items, dim3((unsigned)((n_items * zps + 255) / 256)), dim3(256), 0, s, planar, stage, zps, np_s, cells,
+                     n_items, num_per, nj);
+  launched(0, "k_planar_put_items");
+}
+void launch_planar_read(u64* out, const unsigned char* planar, int plane, int z, int ii, int jl0, int count, int num_per, int nj,
+                        hipStream_t s) {
+  if (count <= 0) return;
+  hipLaunchKernelGGL(k_planar_read, dim3((count + 63) / 64), dim3(64), 0, s, out, planar, (size_t)plane * N + (size_t)z, ii, jl0, count,
+                     num_per, nj);
+  launched(0, "k_planar_read");
+}
+// The group's query tables for a pass over a planar-resident database (d.planar = its words): one tile's planar tables and offset
+// terms for 1 .. 8 queries, both tiles' for 9 .. 16.  No switch is asked: the handle's format was decided when it was created.
+void sweep_planar_resident_prepare(const DevTables& T, SweepBatchDesc& d, hipStream_t s) {
+  if (!d.planar || !d.rq || d.batch < 1 || d.batch > SWEEP_GROUP_MAX) throw HipError("internal: not a group of a planar-resident database");
+  d.use_mfma = 1;
+  if (sweep_batch_tiles(d.batch) == 2) {
+    launch_query_tables_planar2(T, d.qv, d.batch, d.dim0, d.j0, d.nj, d.rq, s);
+    return;
+  }
+  QueryDigitsDesc q{};
+  for (int b = 0; b < d.batch; b++) q.qv[b] = d.qv[b];
+  q.rq = d.rq;
+  q.batch = d.batch;
+  q.dim0 = d.dim0;
+  q.j0 = d.j0;
+  q.nj = d.nj;
+  const size_t entries = (size_t)N * (d.nj >> 4) * 128;
+  launch_query_digits_planar(q, entries, s);
+  hipLaunchKernelGGL(k_query_offset_terms, dim3(N), dim3(256), 0, s, T, q, d.rq + entries * 4);
+  launched(0, "k_query_offset_terms");
+}
+// The pass: 9 .. 16 queries take launch_sweep_planar as it is; 1 .. 8 take the same kernel with ONE query tile: 56 accumulator
+// registers where two tiles hold 112, and half the LDS (nj * 128 bytes: 64 KiB at 512 rows, the default limit, two workgroups of a
+// CU's 160 KiB).  Workgroup shape and ring depth are chosen as for two tiles.  The registers the compiler reports (gfx950, bound of two
+// waves per SIMD): 155 with the ring of 4 units, 125 with the ring of 2 -- three and four waves per SIMD.  Four-wave workgroups
+// therefore run two per CU at 512 rows (LDS-bound) and more at fewer rows; eight-wave workgroups run one per CU with the ring of 4
+// (two waves per SIMD, as the two-tile pass) and two with the ring of 2.  Compiled for four waves per SIMD the ring of 4 spills (212
+// bytes of scratch), so that bound is not asked for.  tests/test_planar_resident_kernel_resources.py holds these numbers.
+void launch_sweep_planar_resident(const DevTables& T, const SweepBatchDesc& d, hipStream_t s) {
+  if (!d.planar || !d.rq || !d.use_mfma) throw HipError("internal: not a prepared group of a planar-resident database");
+  if (sweep_batch_tiles(d.batch) == 2) {
+    launch_sweep_planar(T, d, s);
+    return;
+  }
+  SweepPlanarDesc m{};
+  m.db = d.planar;
+  m.rq = reinterpret_cast<const unsigned char*>(d.rq);
+  m.rq_off = d.rq + (size_t)N * (d.nj >> 4) * 128 * 4;
+  for (int b = 0; b < d.batch; b++) m.out[b] = d.out[b];
+  for (int b = d.batch; b < SWEEP_MFMA_MAX; b++) m.out[b] = d.out[0];   // never stored to (b < batch in the kernel)
+  m.batch = d.batch;
+  m.planes = d.planes;
+  m.num_per = d.num_per;
+  m.nj = d.nj;
+  const int chunks = d.num_per >> 7;
+  int cpw = (int)tunable("batch_mfma_cpw", 16);
+  cpw = std::max(1, std::min(cpw, chunks));
+  while (chunks % cpw) cpw--;
+  m.cpw = cpw;
+  const u64 qs[2] = {MODULUS_0, MODULUS_1};
+  for (int c = 0; c < 2; c++) {
+    m.c4[c] = (u32)((1ull << 32) % qs[c]);
+    m.c5[c] = (u32)((1ull << 40) % qs[c]);
+    m.c6[c] = (u32)((1ull << 48) % qs[c]);
+  }
+  const dim3 grid((unsigned)((size_t)d.planes * N * (chunks / cpw)));
+  const size_t lds = (size_t)d.nj * 128;   // one tile's query planes of one z-row
+  const bool eight = (cpw % 2) == 0;
+  const bool ring4 = ((2 * (d.nj >> 6)) % 4) == 0;
+#define SP_PLANAR1(NBUF_, WAVES_)                                                                                             \
+  {                                                                                                                            \
+    if (lds > 65536)                                                                                                           \
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep_planar<NBUF_, 1, 0, PLANAR1_MINWG, WAVES_>),        \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                    \
+    hipLaunchKernelGGL((k_sweep_planar<NBUF_, 1, 0, PLANAR1_MINWG, WAVES_>), grid, dim3(64 * WAVES_), lds, s, T, m);            \
+  }
+  if (eight && ring4) SP_PLANAR1(4, 8) else if (eight) SP_PLANAR1(2, 8) else if (ring4) SP_PLANAR1(4, 4) else SP_PLANAR1(2, 4)
+#undef SP_PLANAR1
+  launched(PATH_SWEEP_BATCH | PATH_SWEEP_MFMA | PATH_SWEEP_PLANAR, "k_sweep_planar (one query tile)");
 }
 
 }  // namespace spiral

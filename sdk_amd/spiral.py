@@ -410,6 +410,26 @@ class Database:
             raise SpiralError(_err())
         return self
 
+    @classmethod
+    def planar(cls, params, shard=0, num_shards=1):
+        """A planar-resident database (sp_db_create_planar): the digit-planar layout the matrix-core group pass reads is its ONLY
+        resident form (8 bytes per word, no second copy), read by every query of every list size -- for buckets where lists
+        dominate.  dim0 % 64 == 0, dim0 <= 512, num_per % 128 == 0; unsharded only (any other shard request raises)."""
+        if (shard, num_shards) != (0, 1):
+            raise SpiralError("a planar-resident database is unsharded (sp_db_create_planar offers no shards)")
+        self = cls.__new__(cls)
+        self.params, self.shard, self.num_shards, self.by_columns = params, 0, 1, False
+        lib().sp_db_create_planar.restype = C.c_void_p
+        self.h = lib().sp_db_create_planar(_vp(params.h))
+        if not self.h:
+            raise SpiralError(_err())
+        return self
+
+    def format(self):
+        """'packed', 'words8', 'sparse' or 'planar' (sp_db_format)"""
+        lib().sp_db_format.restype = C.c_char_p
+        return lib().sp_db_format(_vp(self.h)).decode()
+
     def sparse_items(self):
         return int(lib().sp_db_sparse_items(_vp(self.h)))
 
