@@ -105,6 +105,20 @@ sp_db_t* sp_db_create_columns(const sp_params_t*, int shard, int num_shards);
  * decode to the item).  Updates must not run concurrently with queries on the same handle (the reference holds a
  * RwLock write guard, bin/server.rs:33,48).  Needs expand_queries and 3 <= t_gsw <= 32. */
 sp_db_t* sp_db_create_sparse(const sp_params_t*);
+/* Row shard `shard` of `num_shards` of a sparse bucket, for the multi-GPU flows: sp_db_create's shard rule (dim0 % num_shards == 0,
+ * num_shards <= SP_MAX_ROW_SHARDS, rows j in [shard * dim0 / num_shards, (shard + 1) * dim0 / num_shards)) and
+ * sp_db_create_sparse's parameter rule; sp_db_create_sparse(p) is (p, 0, 1).  The handle stores only the items whose row
+ * j = item_idx / num_per it holds: sp_db_update_item / _items / _rows skip the others (no slot is taken, sp_db_sparse_items does not
+ * count them, sp_db_update_rows counts them as applied; an index >= num_items is SP_E_ARG on every shard), so every rank can be
+ * handed the same /update-row body.  sp_db_format stays "sparse", sp_db_device_bytes is the local store.  A query begun for the
+ * shard (sp_query_begin_for_db) is expanded for the shard's OCCUPIED rows only -- pruning skips subtrees and changes no value --
+ * and an empty shard of a non-empty bucket works (empty row set, the GSW side still expanded).  sp_query_sweep leaves the plain
+ * partial [plane][r][crt][z][ii] (callers who sum themselves finish with sp_query_finish and its % q); the sp_query_sweep_scatter*
+ * family and sp_process_quer{y,ies}_sharded* take the shard as they take a dense row shard, writing EVERY word of the partial
+ * buffer (zeros for absent columns: the reduce-scatter sums all ranks' words) and folding with lib/server's all-zero shortcuts,
+ * so rank 0's response is lib/server's process_query over the whole SparseDb.  sp_process_query, sp_process_query_batch and
+ * sp_server_* answer a shard with num_shards > 1 as they answer a dense row shard (SP_E_ARG). */
+sp_db_t* sp_db_create_sparse_shard(const sp_params_t*, int shard, int num_shards);
 size_t sp_db_sparse_items(const sp_db_t*); /* items present */
 /* A PLANAR-RESIDENT database: an unsharded handle whose only resident form is the digit-planar layout that the matrix-core
  * group pass reads, [plane][z][128-column chunk][wave g][modulus c][64-row block][tile e][digit a][lane][16 bytes] (8 bytes per
@@ -229,7 +243,9 @@ int sp_process_query_batch(const sp_params_t*, const sp_pp_t* const* pps, const 
  *   fold_local    : % q, from_ntt and the top nu_2 - log2(G) fold levels on this rank's columns
  *                   -> planes 2x1 raw cts at sp_query_local_cts_ptr() (DEVICE, local_cts_words u64)
  *   ...           : caller gathers the G local results on the finishing rank: [g][plane][2][N]
- *   finish_gathered: the last log2(G) fold levels (leaf g = rank g), pack, encode. */
+ *   finish_gathered: the last log2(G) fold levels (leaf g = rank g), pack, encode.
+ * On a sparse row shard (sp_db_create_sparse_shard) the sweeps multiply the shard's present items only, under the snapshot the
+ * query was begun on, and fold_local* / finish_gathered take the all-zero shortcuts of lib/server's fold (fold.rs:38-44). */
 int sp_query_sweep_scatter(sp_query_t*, const sp_db_t*, int G);
 /* The same sweep one (instance, trial) plane per launch, planes in order 0 .. planes-1.  Plane p's region of the
  * partial buffer ([p * partial_words/planes, (p+1) * partial_words/planes)) is laid out [g][r][crt][z][ii / G], so
@@ -244,7 +260,11 @@ int sp_query_sweep_scatter_plane(sp_query_t*, const sp_db_t*, int G, int plane);
  * matrix-core kernel in its scatter form (path bits scatter_out, sweep_batch, sweep_batch_mfma, sweep_batch_scatter); every
  * other group or shape is swept per query inside the same call (the bit sweep_batch_scatter stays clear).  SP_E_ARG, nothing
  * enqueued: column-sharded or unsharded handle with G > 1, G != the handle's shard count, a query begun for other
- * params / rows or not in the 'begun' state. */
+ * params / rows or not in the 'begun' state.
+ * On a sparse row shard (sp_db_create_sparse_shard): a group of 2 .. 8 members that hold ONE snapshot of the shard's index and
+ * reach `sparse_batch_min` shares one pass over the shard's items (k_sweep_sparse_scatter_batch; path bits sweep_sparse,
+ * scatter_out, sparse_group_pass); a group of 1, members begun either side of an upsert, or sparse_batch_min = 0 are swept per
+ * query with their own snapshots inside the same call (sweep_sparse, scatter_out) -- the same words either way. */
 int sp_query_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* shard, int G);
 int sp_query_fold_local(sp_query_t*, const void* reduced_chunk_dev, int G);
 /* The local fold one plane at a time on the query's SECOND stream (sp_query_stream2), planes in order: plane p may
@@ -400,7 +420,9 @@ int sp_bench_sweep_ex(sp_query_t* q, const sp_db_t* db, int iters, int per_plane
 int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, int iters, float* ms_per_pass);
 /* ... and for the pass of sp_query_sweep_scatter_group over a row shard (queries begun for it): layout 1 = the scatter-form
  * pass as the group call launches it, 0 = the existing one-tile pass over the same rows writing the plain [z][ii] layout
- * (comparison only: what the interleaved stores cost).  SP_E_ARG where the group call would sweep per query. */
+ * (comparison only: what the interleaved stores cost).  SP_E_ARG where the group call would sweep per query.
+ * On a sparse row shard (queries begun on one snapshot): layout 1 = k_sweep_sparse_scatter (one query, every plane in one launch)
+ * or k_sweep_sparse_scatter_batch (2 .. 8), layout 0 = k_sweep_sparse / k_sweep_sparse_batch over the same items. */
 int sp_bench_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* shard, int G, int layout, int iters,
                                  float* ms_per_pass);
 

@@ -75,6 +75,7 @@ pub mod sys {
         pub fn sp_db_create(p: *const sp_params_t, shard: c_int, num_shards: c_int) -> *mut sp_db_t;
         pub fn sp_db_create_columns(p: *const sp_params_t, shard: c_int, num_shards: c_int) -> *mut sp_db_t;
         pub fn sp_db_create_sparse(p: *const sp_params_t) -> *mut sp_db_t;
+        pub fn sp_db_create_sparse_shard(p: *const sp_params_t, shard: c_int, num_shards: c_int) -> *mut sp_db_t;
         pub fn sp_db_create_planar(p: *const sp_params_t) -> *mut sp_db_t;
         pub fn sp_db_format(db: *const sp_db_t) -> *const c_char;
         pub fn sp_db_sparse_items(db: *const sp_db_t) -> usize;
@@ -321,6 +322,13 @@ impl Database {
     pub fn sparse(params: &Params) -> Self {
         let h = unsafe { sys::sp_db_create_sparse(params.0) };
         assert!(!h.is_null(), "sp_db_create_sparse: {}", last_error());
+        Database(h)
+    }
+    /// Row shard `shard` of `num_shards` of a sparse bucket (`sp_db_create_sparse_shard`): stores only the items whose row it
+    /// holds, so every rank can be handed the same `/update-row` body; served through the sharded flows.
+    pub fn sparse_shard(params: &Params, shard: i32, num_shards: i32) -> Self {
+        let h = unsafe { sys::sp_db_create_sparse_shard(params.0, shard, num_shards) };
+        assert!(!h.is_null(), "sp_db_create_sparse_shard: {}", last_error());
         Database(h)
     }
     /// A planar-resident database (`sp_db_create_planar`): the digit-planar layout is its only resident form, read by every

@@ -74,6 +74,12 @@ const uint8_t* upload_item(sp_db& d, const uint8_t* data, size_t len) {
 }
 
 
+// does this sparse bucket (or row shard of one, sp_db_create_sparse_shard) store item `idx`?  Its row j = idx / num_per is the shard's
+bool sparse_holds(const sp_db& d, size_t idx) {
+  const size_t j = idx / d.params->p.num_per();
+  return j >= (size_t)d.j0 && j < (size_t)d.j0 + (size_t)d.nj;
+}
+
 // room for `slots` polynomial sets in a sparse bucket's store: amortised doubling from 64, contents preserved (caller holds mu)
 void sparse_reserve(sp_db& d, size_t slots) {
   size_t cap = d.slots_cap;
@@ -121,9 +127,16 @@ std::vector<UpsertWindow> upsert_windows(size_t n_groups, size_t planes, BytesOf
 
 // a sparse bucket: update_many_items (loading.rs:361-377) over sparse_db.rs:42-48 upsert; `recs` hold each index once, in order of
 // first appearance (caller holds mu)
-void upsert_sparse(sp_db& d, const std::vector<UpsertRec>& recs) {
+void upsert_sparse(sp_db& d, const std::vector<UpsertRec>& all) {
   sp_params* h = const_cast<sp_params*>(d.params);
   const Params& p = h->p;
+  std::vector<UpsertRec> own;   // a row shard stores the items of its rows only: the others take no slot
+  if (d.num_shards > 1) {
+    for (const UpsertRec& r : all)
+      if (sparse_holds(d, r.idx)) own.push_back(r);
+  }
+  const std::vector<UpsertRec>& recs = d.num_shards > 1 ? own : all;
+  if (recs.empty()) return;
   DeviceState& D = h->device_state();
   const size_t planes = p.planes();
   // new keys: slots in order of first appearance, the store grown once for all of them, before the first kernel
@@ -562,7 +575,25 @@ static void need_shard_count(const Params& p, int G, const sp_db_t* db = nullptr
   if (!db) return need(ok, "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS)");
   need(ok && db->num_shards == G, "G must be a power of two <= min(num_per, SP_MAX_ROW_SHARDS) and equal to the db's num_shards");
 }
-static void need_row_shard(const sp_db_t* db) { need(db->col_G == 1 && !db->sparse, "sweep_scatter works on row shards"); }
+static void need_row_shard(const sp_db_t* db) { need(db->col_G == 1, "sweep_scatter works on row shards"); }
+// a sparse bucket (or row shard of one) is swept by the queries begun for it, each with the snapshot of the index it was begun on
+static void need_begun_for(const sp_query_t* q, const sp_db_t* db) {
+  need(q->for_sparse == nullptr || q->for_sparse == db, "the query was expanded for another sparse bucket");
+  if (db->sparse) need(q->for_sparse == db && q->sparse_index, "a sparse bucket needs sp_query_begin_for_db(…, db) (its expansion is pruned)");
+}
+// switch sparse_batch_min as the list flow reads it (capi_batch.cpp): the smallest group that shares one pass, 0 = none does
+static int sparse_group_min() {
+  long m = tunable("sparse_batch_min", SPARSE_BATCH_MIN_DEFAULT);
+  if (m < 0) m = SPARSE_BATCH_MIN_DEFAULT;
+  return m == 0 || m > SPARSE_GROUP_MAX ? 0 : (int)std::max(2L, m);
+}
+// one query's scatter sweep over a sparse row shard, planes [plane0, plane0 + n_planes), on its own stream; the folds that follow
+// (sp_query_fold_local*, sp_query_finish_gathered) take lib/server's all-zero shortcuts (fold.rs:38-44)
+static void sweep_sparse_scatter(sp_query_t* q, const sp_db_t* db, int G, int plane0, int n_planes, bool per_plane) {
+  const sp_db::SparseIndex& idx = *q->sparse_index;
+  run_sweep_sparse_scatter(*q->ws, *db, idx.col_ptr.p, idx.col_rows.p, idx.col_slots.p, G, plane0, n_planes, per_plane);
+  q->ws->zero_shortcuts = true;
+}
 // the workspace's first-dimension output in the reduce-scatter layout of G shards while the scope's sweep launches are enqueued:
 // plain again on every path out of it, so that the workspace never goes on to another stage, or back to the pool, in scatter layout
 struct ScatterLayout {
@@ -581,13 +612,14 @@ void spiral::scatter_group_check(sp_query_t* const* qs, int batch, const sp_db_t
     need(qs[i] && qs[i]->ws, "null query");
     need(qs[i]->params == db->params, "db was created for different params");
     need_rows_of(qs[i], db);
+    need_begun_for(qs[i], db);
     for (int k = 0; k < i; k++) need(qs[k] != qs[i], "sp_query_sweep_scatter_group: the same query twice");
   }
   check_device(db->device);
 }
 bool spiral::scatter_group_desc(sp_query_t* const* qs, int batch, const sp_db_t* db, int G, SweepBatchDesc& d) {
   for (int i = 0; i < batch; i++) qs[i]->ws->ensure_sweep();
-  if (!db->packed || G < 2) return false;
+  if (!db->packed || db->sparse || G < 2) return false;
   PlanarPin none;
   d = group_pass(*db, qs, batch, false, none);
   return d.rq != nullptr && sweep_batch_scatter_ok(d, G);
@@ -645,7 +677,11 @@ extern "C" void sp_shard_split_hint_(int on) { g_shard_split_hint = on; }
 // count is one where the batched list measured faster than the pipelined one (switch batch_scatter_max_g; profiles/sharded_batch_pass.md),
 // else 1 = the per-query flow.  Depends on the shard's shape and the switches only: the same answer on every rank.
 extern "C" int sp_scatter_group_choice_(const sp_db_t* db, int G) {
-  if (!db || !db->packed || db->col_G != 1 || db->sparse || db->num_shards != G) return 1;
+  if (db && db->sparse) {   // 8 where the list flow's switch lets a group share one pass over a sparse shard at all
+    tunables_new_call();
+    return db->col_G == 1 && db->num_shards == G && sparse_group_min() != 0 ? SPARSE_GROUP_MAX : 1;
+  }
+  if (!db || !db->packed || db->col_G != 1 || db->num_shards != G) return 1;
   SweepBatchDesc d{};
   d.batch = SWEEP_BATCH_MAX;
   d.num_per = db->np_local;
@@ -774,23 +810,31 @@ static sp_db_t* db_create_impl(const sp_params_t* h, int shard, int num_shards, 
     return d;
   });
 }
-// lib/server's SparseDb (lib/server/src/db/sparse_db.rs:5-48): an empty bucket that stores only the items written to it
-sp_db_t* sp_db_create_sparse(const sp_params_t* h) {
+// lib/server's SparseDb (lib/server/src/db/sparse_db.rs:5-48): an empty bucket that stores only the items written to it -- or, as
+// row shard `shard` of `num_shards` (sp_db_create's rule), only those of them whose row j = item / num_per it holds
+sp_db_t* sp_db_create_sparse_shard(const sp_params_t* h, int shard, int num_shards) {
   return guarded_handle([&] {
     need(h != nullptr, "params is null");
     const Params& p = h->p;
     need(p.expand_queries, "sparse buckets serve expanded queries (lib/server's sparse path, server.rs:31-33)");
     need(fused_fold_supported(p), "sparse buckets need gadget parameters the fused fold supports (3 <= t_gsw <= 32)");
+    need(num_shards >= 1 && shard >= 0 && shard < num_shards, "bad shard");
+    need(p.dim0() % (size_t)num_shards == 0, "dim0 not divisible by num_shards");
+    need(num_shards <= SP_MAX_ROW_SHARDS, "at most SP_MAX_ROW_SHARDS (8) row shards: the partial residues are summed in 32 bits");
     auto d = std::make_unique<sp_db>();
     d->params = h;
     HIP_CHECK(hipGetDevice(&d->device));
     d->sparse = true;
-    d->nj = (int)p.dim0();
+    d->shard = shard;
+    d->num_shards = num_shards;
+    d->nj = (int)(p.dim0() / num_shards);
+    d->j0 = shard * d->nj;
     d->np_local = (int)p.num_per();
     const_cast<sp_params*>(h)->device_state();
     return d;
   });
 }
+sp_db_t* sp_db_create_sparse(const sp_params_t* h) { return sp_db_create_sparse_shard(h, 0, 1); }
 // A database whose only resident form is the digit-planar layout (sweep_planar.hpp): one copy of 8 bytes per word that every query
 // of every list size reads.  Unsharded; the empty database (all-zero polynomials) is every byte 0x80, the offset digit of 0.
 sp_db_t* sp_db_create_planar(const sp_params_t* h) {
@@ -971,6 +1015,7 @@ int sp_db_update_item(sp_db_t* d, size_t item_idx, const uint8_t* data, size_t l
     need(len <= p.db_item_size, "item longer than db_item_size");
     if (d->sparse) {
       // lib/server/src/db/loading.rs:317-359 update_item_raw + sparse_db.rs:42-48 upsert
+      if (!sparse_holds(*d, item_idx)) return;   // the row lives on another shard: no slot is taken
       DeviceState& D = h->device_state();
       std::lock_guard<std::mutex> lk(d->mu);
       const size_t planes = p.planes(), poly_words = planes * POLY_LEN;
@@ -1274,10 +1319,15 @@ int sp_query_sweep_scatter(sp_query_t* q, const sp_db_t* db, int G) {
     need_rows_of(q, db);
     need_shard_count(q->params->p, G, db);
     need_row_shard(db);
+    need_begun_for(q, db);
     check_device(db->device);
     Workspace& W = *q->ws;
-    ScatterLayout scatter(W, G);
-    run_sweep(W, *db);
+    if (db->sparse) {   // chunk-major: chunk g = [plane][r][crt][z][ii / G]
+      sweep_sparse_scatter(q, db, G, 0, (int)q->params->p.planes(), false);
+    } else {
+      ScatterLayout scatter(W, G);
+      run_sweep(W, *db);
+    }
     HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
     q->state = 2;
   });
@@ -1292,13 +1342,18 @@ int sp_query_sweep_scatter_plane(sp_query_t* q, const sp_db_t* db, int G, int pl
     const Params& p = q->params->p;
     need_shard_count(p, G, db);
     need_row_shard(db);
+    need_begun_for(q, db);
     need(plane >= 0 && (size_t)plane < p.planes(), "plane out of range");
     need(q->state == 1 && q->next_plane == plane, "sp_query_sweep_scatter_plane: planes must be swept in order after begin");
     check_device(db->device);
     Workspace& W = *q->ws;
     W.ensure_sweep();
-    ScatterLayout scatter(W, G);
-    launch_plane_sweep(W, *db, (size_t)plane);
+    if (db->sparse) {
+      sweep_sparse_scatter(q, db, G, plane, 1, true);
+    } else {
+      ScatterLayout scatter(W, G);
+      launch_plane_sweep(W, *db, (size_t)plane);
+    }
     q->next_plane = plane + 1;
     if ((size_t)q->next_plane == p.planes()) {
       HIP_CHECK(hipEventRecord(W.ev[2], W.stream));
@@ -1316,7 +1371,31 @@ int sp_query_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t
       need(qs[i]->state == 1 && qs[i]->next_plane == 0, "sp_query_sweep_scatter_group: every query must be in 'begun' state, no plane swept");
     const size_t planes = db->params->p.planes();
     SweepBatchDesc d{};
-    if (scatter_group_desc(qs, batch, db, G, d)) {
+    if (db->sparse) {
+      // a sparse row shard: one pass (k_sweep_sparse_scatter_batch) for a group of at least `sparse_batch_min` members that hold ONE
+      // snapshot of the shard's index; a single query, members begun either side of an upsert or the switch at 0: each member's
+      // own sweep with its own snapshot, the same words.  Decided from the switch and the handles, never from the occupancy.
+      const int group_min = sparse_group_min();
+      bool shared = batch >= 2 && group_min != 0 && batch >= group_min;
+      for (int i = 1; i < batch; i++) shared = shared && qs[i]->sparse_index == qs[0]->sparse_index;
+      for (int i = 0; i < batch; i++) qs[i]->ws->ensure_sweep();   // every buffer before anything is enqueued
+      if (shared) {
+        Workspace* Ws[SPARSE_GROUP_MAX];
+        for (int i = 0; i < batch; i++) Ws[i] = qs[i]->ws.get();
+        const sp_db::SparseIndex& idx = *qs[0]->sparse_index;
+        Workspace& W0 = group_pass_stream(qs, batch);
+        run_sweep_sparse_scatter_group(Ws, batch, *db, idx.col_ptr.p, idx.col_rows.p, idx.col_slots.p, G, W0.stream);
+        for (int i = 0; i < batch; i++) {
+          group_pass_done(qs, i);
+          qs[i]->ws->zero_shortcuts = true;
+        }
+      } else {
+        for (int i = 0; i < batch; i++) {
+          sweep_sparse_scatter(qs[i], db, G, 0, (int)planes, true);
+          HIP_CHECK(hipEventRecord(qs[i]->ws->ev[2], qs[i]->ws->stream));
+        }
+      }
+    } else if (scatter_group_desc(qs, batch, db, G, d)) {
       // ordered after every query's expansion (ev[1], recorded by sp_query_begin_for_db) ...
       Workspace& W0 = group_pass_stream(qs, batch);
       sweep_batch_prepare(W0.D->T, d, W0.stream);

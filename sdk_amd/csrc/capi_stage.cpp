@@ -142,6 +142,30 @@ int sp_bench_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t
       HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream));   // expansions done: the pass is timed alone
       HIP_CHECK(hipStreamSynchronize(qs[i]->ws->stream2));
     }
+    if (db->sparse) {
+      // a sparse row shard, members of one snapshot: the scatter-form kernels (one query: k_sweep_sparse_scatter, every plane in one
+      // launch; 2 .. 8: k_sweep_sparse_scatter_batch) or, layout 0, the plain-layout kernels over the same items (comparison only)
+      Workspace* Ws[SPARSE_GROUP_MAX];
+      for (int i = 0; i < batch; i++) {
+        need(qs[i]->sparse_index == qs[0]->sparse_index, "the queries of a sparse bucket's group must have been begun on one snapshot of its index");
+        qs[i]->ws->ensure_sweep();
+        Ws[i] = qs[i]->ws.get();
+      }
+      const sp_db::SparseIndex& idx = *qs[0]->sparse_index;
+      Workspace& W0 = *qs[0]->ws;
+      const int planes = (int)db->params->p.planes();
+      *ms_per_pass = timed_reps(W0.stream, iters, [&] {
+        if (batch == 1 && layout == 1)
+          run_sweep_sparse_scatter(W0, *db, idx.col_ptr.p, idx.col_rows.p, idx.col_slots.p, G, 0, planes, true);
+        else if (batch == 1)
+          run_sweep_sparse(W0, *db, idx.col_ptr.p, idx.col_rows.p, idx.col_slots.p);
+        else if (layout == 1)
+          run_sweep_sparse_scatter_group(Ws, batch, *db, idx.col_ptr.p, idx.col_rows.p, idx.col_slots.p, G, W0.stream);
+        else
+          run_sweep_sparse_group(Ws, batch, *db, idx.col_ptr.p, idx.col_rows.p, idx.col_slots.p, W0.stream);
+      });
+      return;
+    }
     SweepBatchDesc d{};
     need(scatter_group_desc(qs, batch, db, G, d), "this group / shard does not take the scatter-form pass (sp_query_sweep_scatter_group would sweep per query)");
     Workspace& W0 = *qs[0]->ws;

@@ -572,6 +572,15 @@ struct SparseGroup {
 };
 void launch_sweep_sparse_batch(const DevTables& T, const int* col_ptr, const int* col_rows, const int* col_slots, const u64* polys,
                                int planes, const SparseGroup& members, int nq, int first, int step, int num_per, hipStream_t s);
+// ... and on a ROW SHARD of a sparse bucket (col_rows hold global rows), output in the reduce-scatter layouts of G ranks
+// (sweep_sparse_scatter.hpp): planes [plane0, plane0 + n_planes) of one query, chunk-major or (per_plane) in the per-plane form;
+// every plane of a group of 1 .. SPARSE_GROUP_MAX queries in one pass, per-plane form.  Every word is written, zeros included.
+void launch_sweep_sparse_scatter(const DevTables& T, const int* col_ptr, const int* col_rows, const int* col_slots, const u64* polys,
+                                 int planes, int plane0, int n_planes, const u32* v, int first, int step, u32* out, int num_per, int G,
+                                 bool per_plane, hipStream_t s);
+void launch_sweep_sparse_scatter_batch(const DevTables& T, const int* col_ptr, const int* col_rows, const int* col_slots, const u64* polys,
+                                       int planes, const SparseGroup& members, int nq, int first, int step, int num_per, int G,
+                                       hipStream_t s);
 
 // sweep-native out [plane][r][crt][z][ii] -> reference out[ii].data[r*2N + crt*N + z] (u64) for one plane
 void launch_sweep_out_to_ref(u64* out, const u32* in, int num_per, hipStream_t s);

@@ -85,6 +85,12 @@ void run_sweep_sparse(Workspace& W, const sp_db& db, const int* col_ptr, const i
 // ... for the workspaces of a group of up to SPARSE_GROUP_MAX queries in one pass (every item word read once), enqueued on `s`
 void run_sweep_sparse_group(Workspace* const* Ws, int B, const sp_db& db, const int* col_ptr, const int* col_rows, const int* col_slots,
                             hipStream_t s);
+// ... on a ROW SHARD of a sparse bucket, in the reduce-scatter layouts of G ranks: planes [plane0, plane0 + n_planes) of one query on its
+// own stream (per_plane: the per-plane exchange form, else chunk-major), and every plane of a group in one pass (per-plane form) on `s`
+void run_sweep_sparse_scatter(Workspace& W, const sp_db& db, const int* col_ptr, const int* col_rows, const int* col_slots, int G,
+                              int plane0, int n_planes, bool per_plane);
+void run_sweep_sparse_scatter_group(Workspace* const* Ws, int B, const sp_db& db, const int* col_ptr, const int* col_rows,
+                                    const int* col_slots, int G, hipStream_t s);
 // expansion schedule pruned to an arbitrary set of first-dimension rows (rows[j] != 0), lists uploaded
 std::unique_ptr<DeviceState::PrunedPlan> build_pruned_plan_rows(const Params& P, const std::vector<char>& rows);
 void run_sweep(Workspace& W, const sp_db& db);

@@ -1284,6 +1284,28 @@ void run_sweep_sparse_group(Workspace* const* Ws, int B, const sp_db& db, const 
                             (int)p.num_per(), s);
 }
 
+// the two products on a row shard of a sparse bucket (the index holds the shard's items under their GLOBAL rows), stored where the
+// reduce-scatter of G ranks expects them; every word of the planes swept is written
+void run_sweep_sparse_scatter(Workspace& W, const sp_db& db, const int* col_ptr, const int* col_rows, const int* col_slots, int G,
+                              int plane0, int n_planes, bool per_plane) {
+  const Params& p = *W.P;
+  W.ensure_sweep();
+  launch_sweep_sparse_scatter(W.D->T, col_ptr, col_rows, col_slots, db.polys.p, (int)p.planes(), plane0, n_planes, W.v.p, 0,
+                              p.db_dim_2 > 0 ? 2 : 1, W.sweep_out.p, (int)p.num_per(), G, per_plane, W.stream);
+}
+void run_sweep_sparse_scatter_group(Workspace* const* Ws, int B, const sp_db& db, const int* col_ptr, const int* col_rows,
+                                    const int* col_slots, int G, hipStream_t s) {
+  const Params& p = *Ws[0]->P;
+  SparseGroup g{};
+  for (int b = 0; b < B; b++) {
+    Ws[b]->ensure_sweep();
+    g.v[b] = Ws[b]->v.p;
+    g.out[b] = Ws[b]->sweep_out.p;
+  }
+  launch_sweep_sparse_scatter_batch(Ws[0]->D->T, col_ptr, col_rows, col_slots, db.polys.p, (int)p.planes(), g, B, 0,
+                                    p.db_dim_2 > 0 ? 2 : 1, (int)p.num_per(), G, s);
+}
+
 // The query flows' fold: the workspace's threshold (read when it was created: the digit staging of the unfused levels is sized
 // from it), lowered -- never raised -- by the run-time switch fused_min_pairs_cap (in-process A/B); delta-form tail.  below_q only
 // for ciphertexts this library has just produced itself (from_ntt / fold outputs): everything else (ciphertexts gathered from

@@ -279,3 +279,6 @@ void launch_sweep_sparse_batch(const DevTables& T, const int* col_ptr, const int
 }
 
 }  // namespace spiral
+
+// the same multiplies on a row shard of a sparse bucket, stored in the reduce-scatter layouts
+#include "sweep_sparse_scatter.hpp"

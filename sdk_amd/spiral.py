@@ -398,14 +398,16 @@ class Database:
             pass
 
     @classmethod
-    def sparse(cls, params):
+    def sparse(cls, params, shard=0, num_shards=1):
         """lib/server's SparseDb (db/sparse_db.rs:5-48): an empty bucket that stores (and multiplies) only the items
-        written through update_item; process_query on it follows lib/server/src/server.rs:17-99."""
+        written through update_item; process_query on it follows lib/server/src/server.rs:17-99.  shard / num_shards: row shard
+        `shard` of `num_shards` (sp_db_create_sparse_shard), which keeps only the items of its rows and is served through the
+        sweep_scatter family and the Comm flows."""
         self = cls.__new__(cls)
-        self.params, self.shard, self.num_shards, self.by_columns = params, 0, 1, False
-        lib().sp_db_create_sparse.restype = C.c_void_p
+        self.params, self.shard, self.num_shards, self.by_columns = params, shard, num_shards, False
+        lib().sp_db_create_sparse_shard.restype = C.c_void_p
         lib().sp_db_sparse_items.restype = C.c_size_t
-        self.h = lib().sp_db_create_sparse(_vp(params.h))
+        self.h = lib().sp_db_create_sparse_shard(_vp(params.h), C.c_int(shard), C.c_int(num_shards))
         if not self.h:
             raise SpiralError(_err())
         return self
