@@ -133,6 +133,25 @@ size_t sp_db_sparse_items(const sp_db_t*); /* items present */
  * 1, sp_db_batch_copy_bytes is 0.  The sp_query_sweep_scatter* family, sp_process_quer{y,ies}_sharded* and sp_bench_sweep[_ex]
  * refuse it with SP_E_ARG ("planar-resident"). */
 sp_db_t* sp_db_create_planar(const sp_params_t*);
+/* A PLANAR ROW SHARD: row shard `shard` of `num_shards` (2, 4 or 8; sp_db_create's rule: rows j in [shard * dim0 / S,
+ * (shard + 1) * dim0 / S)) whose only resident form is the digit-planar layout.  It is what lets a sharded LIST take the 16-query pass:
+ * sp_query_sweep_scatter_group and sp_process_queries_sharded_batched take 1 .. 16 queries per pass on it (1 .. 8 on every other
+ * shard), and the pass over 16 costs about what the pass over 8 costs.  Cost: 8 bytes per word resident instead of 7, so a single
+ * sharded query reads 14 % more than on a PACKED shard; choose it where lists dominate.
+ * Shapes (sp_db_create_planar's rule on the LOCAL rows): nj = dim0 / S a multiple of 64 and <= 512, num_per % 128 == 0; the switches
+ * batch_planar and batch_mfma must be on at creation (all else SP_E_ARG); num_shards == 1 is SP_E_ARG (use sp_db_create_planar, which
+ * the sharded entry points keep refusing, G = 1 included).  sp_db_format is "planar", sp_db_device_bytes the local words at 8 bytes.
+ * Resident column order: local column ii is stored at resident column (ii % S) * (num_per / S) + ii / S, so the columns that go to
+ * one rank of the exchange are one contiguous run and the pass stores the reduce-scatter layout in the same 128-byte runs as the
+ * plain one; sp_db_read_ref and every writer keep speaking reference coordinates.
+ * sp_db_load, _load_plane, _load_items, _fill_synthetic, _update_item, _update_items, _update_rows and _read_ref work as on a dense
+ * PACKED row shard: the loaders are handed full-dim0 rows and keep the shard's, upserts of rows the shard does not hold are skipped
+ * (and counted as applied), so every rank takes the same /update-row body.  No buffer of the shard's size other than the planar words
+ * ever exists.  Queries: sp_query_begin_for_db, then the sp_query_sweep_scatter* family (below) and sp_process_quer{y,ies}_sharded*;
+ * sp_query_sweep (the plain partial) REFUSES a planar row shard (SP_E_ARG: its column order is the exchange's), and so does
+ * sp_bench_sweep[_ex] ("planar-resident", as on the unsharded handle; sp_bench_sweep_scatter_group times its pass); sp_process_query,
+ * sp_process_query_batch, sp_bench_sweep_batch and sp_server_* answer it as they answer any row shard (SP_E_ARG). */
+sp_db_t* sp_db_create_planar_shard(const sp_params_t*, int shard, int num_shards);
 /* "packed" (7-byte words), "words8" (8-byte words), "sparse" or "planar"; no device call */
 const char* sp_db_format(const sp_db_t*);
 void sp_db_free(sp_db_t*);
@@ -245,7 +264,10 @@ int sp_process_query_batch(const sp_params_t*, const sp_pp_t* const* pps, const 
  *   ...           : caller gathers the G local results on the finishing rank: [g][plane][2][N]
  *   finish_gathered: the last log2(G) fold levels (leaf g = rank g), pack, encode.
  * On a sparse row shard (sp_db_create_sparse_shard) the sweeps multiply the shard's present items only, under the snapshot the
- * query was begun on, and fold_local* / finish_gathered take the all-zero shortcuts of lib/server's fold (fold.rs:38-44). */
+ * query was begun on, and fold_local* / finish_gathered take the all-zero shortcuts of lib/server's fold (fold.rs:38-44).
+ * On a planar row shard (sp_db_create_planar_shard) sweep_scatter and sweep_scatter_plane run the group pass of
+ * sp_query_sweep_scatter_group for a group of one (k_sweep_planar_scatter, one query tile; _plane launches that plane's z-range) and
+ * leave the same words as on a PACKED shard of the same content. */
 int sp_query_sweep_scatter(sp_query_t*, const sp_db_t*, int G);
 /* The same sweep one (instance, trial) plane per launch, planes in order 0 .. planes-1.  Plane p's region of the
  * partial buffer ([p * partial_words/planes, (p+1) * partial_words/planes)) is laid out [g][r][crt][z][ii / G], so
@@ -264,7 +286,12 @@ int sp_query_sweep_scatter_plane(sp_query_t*, const sp_db_t*, int G, int plane);
  * On a sparse row shard (sp_db_create_sparse_shard): a group of 2 .. 8 members that hold ONE snapshot of the shard's index and
  * reach `sparse_batch_min` shares one pass over the shard's items (k_sweep_sparse_scatter_batch; path bits sweep_sparse,
  * scatter_out, sparse_group_pass); a group of 1, members begun either side of an upsert, or sparse_batch_min = 0 are swept per
- * query with their own snapshots inside the same call (sweep_sparse, scatter_out) -- the same words either way. */
+ * query with their own snapshots inside the same call (sweep_sparse, scatter_out) -- the same words either way.
+ * On a planar row shard (sp_db_create_planar_shard): 1 .. 16 queries per pass (1 .. 8 where the device does not offer two query
+ * tiles' tables, nj * 256 bytes of LDS, to one workgroup; batch > 8 on any other shard stays SP_E_ARG), always ONE launch of
+ * k_sweep_planar_scatter -- one query tile for 1 .. 8, two for 9 .. 16.  Path bits: scatter_out, sweep_batch, sweep_batch_mfma,
+ * sweep_batch_planar, plus sweep_batch_mfma_two_tiles for 9 .. 16 -- no other flow reports scatter_out together with
+ * sweep_batch_planar; sweep_batch_scatter stays clear (it names the PACKED shards' k_sweep_mfma_scatter). */
 int sp_query_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* shard, int G);
 int sp_query_fold_local(sp_query_t*, const void* reduced_chunk_dev, int G);
 /* The local fold one plane at a time on the query's SECOND stream (sp_query_stream2), planes in order: plane p may
@@ -284,6 +311,7 @@ sp_query_t* sp_query_begin(const sp_params_t*, const sp_pp_t*, const uint8_t* qu
  * db == NULL, unsharded or column-sharded: identical to sp_query_begin. */
 sp_query_t* sp_query_begin_for_db(const sp_params_t*, const sp_pp_t*, const uint8_t* query, size_t query_len,
                                   const sp_db_t* db);
+/* (a planar row shard, sp_db_create_planar_shard, is refused with SP_E_ARG: it has the scatter-form sweeps only) */
 int sp_query_sweep(sp_query_t*, const sp_db_t*);
 void* sp_query_partial_ptr(sp_query_t*);
 size_t sp_query_partial_words(const sp_query_t*);
@@ -330,7 +358,9 @@ int sp_comm_world(const sp_comm_t*);
 void* sp_comm_stream(sp_comm_t*); /* hipStream_t the collectives are enqueued on */
 int sp_comm_barrier(sp_comm_t*);  /* one tiny all-gather + host wait: every rank has reached this call */
 /* process_query (server.rs:650-741) over a row-sharded database; `shard` = this rank's sp_db_create(params, rank,
- * world).  Byte-identical to sp_process_query over the unsharded database. */
+ * world) -- or sp_db_create_sparse_shard / sp_db_create_planar_shard(params, rank, world): the same bytes.  Byte-identical to
+ * sp_process_query over the unsharded database.  A planar row shard of another shard count than the communicator's world is
+ * SP_E_ARG before anything is enqueued (here and in the two list calls). */
 int sp_process_query_sharded(sp_comm_t*, const sp_params_t*, const sp_pp_t*, const uint8_t* query, size_t query_len,
                              const sp_db_t* shard, uint8_t* out, size_t out_cap, size_t* out_len);
 /* The same for a LIST of queries (what a /private-read request carries, lib/server/src/bin/server.rs:152-158),
@@ -347,12 +377,19 @@ int sp_process_queries_sharded(sp_comm_t*, const sp_params_t*, const sp_pp_t* co
  * 0, sp_query_finish_gathered.  group: 1 .. 8, or 0 = the library's choice (8 where the scatter-form pass applies to the
  * shard, else the per-query flow of sp_process_queries_sharded).  The sequence of collectives is a function of (n, group,
  * params, shard shape) alone, so every rank issues the same one.  Every query's length is checked before anything is begun:
- * a bad list enters no collective.  Same outputs and the same bytes as sp_process_queries_sharded. */
+ * a bad list enters no collective.  Same outputs and the same bytes as sp_process_queries_sharded.
+ * On a planar row shard (sp_db_create_planar_shard) group is 1 .. 16, and 0 = 16 where the shard's shape allows two query tiles
+ * (nj * 256 bytes of LDS per workgroup), otherwise 8; group > 8 on any other shard stays SP_E_ARG.  (The out-of-memory ladder of
+ * sp_process_query_batch is NOT part of this call: a rank that stepped its group size down alone would issue another sequence of
+ * collectives than its peers.  SP_E_OOM is returned; reserve with sp_comm_reserve_batch_for up front.) */
 int sp_process_queries_sharded_batched(sp_comm_t*, const sp_params_t*, const sp_pp_t* const* pps, const uint8_t* const* queries,
                                        const size_t* query_lens, int n, const sp_db_t* shard, int group, uint8_t* out,
                                        size_t out_stride, size_t* out_len);
 /* sp_comm_reserve plus the receive / gather buffers and events of a group of `group` (1 .. 8; 0 = 8) queries. */
 int sp_comm_reserve_batch(sp_comm_t*, const sp_params_t* params, int group);
+/* The same for the groups a batched list takes on `shard`: group 1 .. the shard's largest (16 on a planar row shard whose shape
+ * allows two query tiles, else 8), 0 = that largest; beyond it SP_E_ARG. */
+int sp_comm_reserve_batch_for(sp_comm_t*, const sp_params_t* params, const sp_db_t* shard, int group);
 /* Allocates the communicator's exchange buffers and events for `params` now, so that no sharded query allocates
  * anything (otherwise the first query with new params does).  Not a collective. */
 int sp_comm_reserve(sp_comm_t*, const sp_params_t* params);
@@ -422,7 +459,9 @@ int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, in
  * pass as the group call launches it, 0 = the existing one-tile pass over the same rows writing the plain [z][ii] layout
  * (comparison only: what the interleaved stores cost).  SP_E_ARG where the group call would sweep per query.
  * On a sparse row shard (queries begun on one snapshot): layout 1 = k_sweep_sparse_scatter (one query, every plane in one launch)
- * or k_sweep_sparse_scatter_batch (2 .. 8), layout 0 = k_sweep_sparse / k_sweep_sparse_batch over the same items. */
+ * or k_sweep_sparse_scatter_batch (2 .. 8), layout 0 = k_sweep_sparse / k_sweep_sparse_batch over the same items.
+ * On a planar row shard: layout 1 = k_sweep_planar_scatter for 1 .. 16 queries (tables + pass); layout 0 is SP_E_ARG (the plain
+ * form over `nj` rows is sp_bench_sweep_batch on an unsharded planar database of that many rows). */
 int sp_bench_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t* shard, int G, int layout, int iters,
                                  float* ms_per_pass);
 

@@ -77,6 +77,7 @@ pub mod sys {
         pub fn sp_db_create_sparse(p: *const sp_params_t) -> *mut sp_db_t;
         pub fn sp_db_create_sparse_shard(p: *const sp_params_t, shard: c_int, num_shards: c_int) -> *mut sp_db_t;
         pub fn sp_db_create_planar(p: *const sp_params_t) -> *mut sp_db_t;
+        pub fn sp_db_create_planar_shard(p: *const sp_params_t, shard: c_int, num_shards: c_int) -> *mut sp_db_t;
         pub fn sp_db_format(db: *const sp_db_t) -> *const c_char;
         pub fn sp_db_sparse_items(db: *const sp_db_t) -> usize;
         pub fn sp_db_free(db: *mut sp_db_t);
@@ -142,6 +143,7 @@ pub mod sys {
                                           out_len: *mut usize) -> c_int;
         pub fn sp_comm_reserve(c: *mut sp_comm_t, p: *const sp_params_t) -> c_int;
         pub fn sp_comm_reserve_batch(c: *mut sp_comm_t, p: *const sp_params_t, group: c_int) -> c_int;
+        pub fn sp_comm_reserve_batch_for(c: *mut sp_comm_t, p: *const sp_params_t, shard: *const sp_db_t, group: c_int) -> c_int;
         pub fn sp_process_queries_sharded_batched(c: *mut sp_comm_t, p: *const sp_params_t, pps: *const *const sp_pp_t,
                                                   queries: *const *const u8, query_lens: *const usize, n: c_int,
                                                   shard: *const sp_db_t, group: c_int, out: *mut u8, out_stride: usize,

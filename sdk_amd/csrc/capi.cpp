@@ -256,13 +256,22 @@ void upsert_dense(sp_db& d, const std::vector<UpsertRec>& recs) {
 // planar positions from there (planar_resident.hpp); no buffer of the database's size other than the planar words ever exists
 constexpr size_t PLANAR_STAGE_BYTES = (size_t)64 << 20;   // 8-byte words staged per launch, at most (one item or column at least)
 unsigned char* planar_words(sp_db& d) { return reinterpret_cast<unsigned char*>(d.words.p); }
+// the handle as the writers of planar_resident.hpp take it: its row window and, on a row shard (sp_db_create_planar_shard), the
+// resident column order of a shard of num_shards
+PlanarShardShape planar_shape(const sp_db& d) { return PlanarShardShape{(int)d.params->p.dim0(), d.j0, d.num_shards}; }
 
 // upserts: `recs` hold each index once.  Per window the existing list encoder (k_db_encode_quads: chunks, log2(p)-bit coefficients,
 // recenter_mod, forward NTT) writes the items' words as an 8-byte database of two rows in the upload buffer -- item r of the window is
 // entry r & 3 of quad r >> 2 -- and k_planar_put_items stores each word's 8 digit bytes.  The device image of a window is
 // [quad table | cell table | item bytes | staged words], each part from a 16-byte boundary (caller holds mu)
-void upsert_planar(sp_db& d, const std::vector<UpsertRec>& recs) {
+void upsert_planar(sp_db& d, const std::vector<UpsertRec>& all) {
   sp_params* h = const_cast<sp_params*>(d.params);
+  // a row shard keeps the records of its rows (the others are some other rank's: skipped, and counted as applied by the callers)
+  std::vector<UpsertRec> recs;
+  recs.reserve(all.size());
+  for (const UpsertRec& r : all)
+    if (sparse_holds(d, r.idx)) recs.push_back(r);
+  if (recs.empty()) return;
   const Params& p = h->p;
   DeviceState& D = h->device_state();
   const size_t planes = p.planes(), word_bytes = planes * POLY_LEN * 8;   // staged bytes of one item
@@ -306,7 +315,7 @@ void upsert_planar(sp_db& d, const std::vector<UpsertRec>& recs) {
       table[r >> 2].len[r & 3] = (int)rec.len;
       if (rec.len) memcpy(host.data() + bytes0 + off, rec.data, rec.len);
       off += rec.len;
-      cells[r] = PlanarPatchCell{(int)(rec.idx / p.num_per()), (int)(rec.idx % p.num_per())};
+      cells[r] = PlanarPatchCell{(int)(rec.idx / p.num_per()) - d.j0, (int)(rec.idx % p.num_per())};
     }
     h2d_sync(d.upload.p, host.data(), stage0);
     u64* stage = reinterpret_cast<u64*>(d.upload.p + stage0);
@@ -320,7 +329,7 @@ void upsert_planar(sp_db& d, const std::vector<UpsertRec>& recs) {
     e.win = d.upload.p + bytes0;
     launch_db_encode_quads(D.T, e, reinterpret_cast<const DbQuadRec*>(d.upload.p), np_s / 2, 0);
     launch_planar_put_items(planar_words(d), stage, (int)planes, np_s, reinterpret_cast<const PlanarPatchCell*>(d.upload.p + cells0), w.groups,
-                            d.np_local, d.nj, 0);   // same stream, after the encode
+                            d.np_local, d.nj, planar_shape(d), 0);   // same stream, after the encode
     HIP_CHECK(hipDeviceSynchronize());
   }
 }
@@ -400,6 +409,27 @@ void spiral::group_pass_launch(const sp_db& db, const DevTables& T, SweepBatchDe
 void spiral::refuse_planar_resident(const sp_db_t* db, const char* what) {
   if (db && db->planar_resident)
     throw ArgError(std::string(what) + " does not take a planar-resident database (sp_db_create_planar): its words are read by the group pass only");
+}
+// the scatter sweeps take a planar ROW SHARD (sp_db_create_planar_shard) and keep refusing the unsharded handle, G = 1 included
+static void refuse_planar_unsharded(const sp_db_t* db, const char* what) {
+  if (db && db->num_shards == 1) refuse_planar_resident(db, what);
+}
+// `B` begun queries' pass over a planar row shard on qs[0]'s stream, ordered after every expansion: planes [plane0, plane0 + n_planes)
+// in the per-plane layout, or all of them in sp_query_sweep_scatter's (all_planes).  The group's query tables are built in front of
+// plane 0 and stay in qs[0]'s workspace for the planes that follow.  The caller orders the members' streams after it (group_pass_done).
+static void planar_shard_pass(sp_query_t* const* qs, int B, const sp_db_t* db, int G, int plane0, int n_planes, bool all_planes) {
+  const int planes = (int)db->params->p.planes();
+  for (int i = 0; i < B; i++) qs[i]->ws->ensure_sweep();   // every buffer before anything is enqueued
+  PlanarPin none;
+  SweepBatchDesc d = group_pass(*db, qs, B, false, none);
+  d.planes = n_planes;
+  d.planar += sweep_planar_bytes(1, db->np_local, db->nj) * (size_t)plane0;
+  Workspace& W0 = group_pass_stream(qs, B);
+  if (plane0 == 0)
+    sweep_planar_resident_prepare(W0.D->T, d, W0.stream);
+  else
+    d.use_mfma = 1;
+  launch_sweep_planar_scatter(W0.D->T, d, G, plane0, planes, all_planes, W0.stream);
 }
 Workspace& spiral::group_pass_stream(sp_query_t* const* qs, int B) {
   Workspace& W0 = *qs[0]->ws;
@@ -604,8 +634,13 @@ struct ScatterLayout {
 
 void spiral::scatter_group_check(sp_query_t* const* qs, int batch, const sp_db_t* db, int G) {
   need(qs && db, "null argument");
-  refuse_planar_resident(db, "sp_query_sweep_scatter_group");
-  need(batch >= 1 && batch <= SWEEP_BATCH_MAX, "sp_query_sweep_scatter_group: 1 .. 8 queries per pass");
+  refuse_planar_unsharded(db, "sp_query_sweep_scatter_group");
+  if (db->planar_resident)   // a planar row shard: both query tiles where the device offers their LDS to one workgroup
+    need(batch >= 1 && batch <= planar_resident_group_max(db->nj), "sp_query_sweep_scatter_group: 1 .. 16 queries per pass over a planar row shard "
+                                                                   "(1 .. 8 where two query tiles' tables do not fit one workgroup's LDS)");
+  else
+    need(batch >= 1 && batch <= SWEEP_BATCH_MAX, "sp_query_sweep_scatter_group: 1 .. 8 queries per pass (1 .. 16 over a planar row shard, "
+                                                 "sp_db_create_planar_shard)");
   need_row_shard(db);
   need_shard_count(db->params->p, G, db);
   for (int i = 0; i < batch; i++) {
@@ -619,7 +654,7 @@ void spiral::scatter_group_check(sp_query_t* const* qs, int batch, const sp_db_t
 }
 bool spiral::scatter_group_desc(sp_query_t* const* qs, int batch, const sp_db_t* db, int G, SweepBatchDesc& d) {
   for (int i = 0; i < batch; i++) qs[i]->ws->ensure_sweep();
-  if (!db->packed || db->sparse || G < 2) return false;
+  if (!db->packed || db->sparse || G < 2) return false;   // (a planar row shard has its own pass: planar_shard_pass)
   PlanarPin none;
   d = group_pass(*db, qs, batch, false, none);
   return d.rq != nullptr && sweep_batch_scatter_ok(d, G);
@@ -681,6 +716,8 @@ extern "C" int sp_scatter_group_choice_(const sp_db_t* db, int G) {
     tunables_new_call();
     return db->col_G == 1 && db->num_shards == G && sparse_group_min() != 0 ? SPARSE_GROUP_MAX : 1;
   }
+  // a planar row shard: 16 where the shape allows two query tiles, else 8 (the handle's format was decided when it was created)
+  if (db && db->planar_resident) return db->num_shards == G && G > 1 ? planar_resident_group_max(db->nj) : 1;
   if (!db || !db->packed || db->col_G != 1 || db->num_shards != G) return 1;
   SweepBatchDesc d{};
   d.batch = SWEEP_BATCH_MAX;
@@ -689,6 +726,11 @@ extern "C" int sp_scatter_group_choice_(const sp_db_t* db, int G) {
   tunables_new_call();
   return sweep_batch_scatter_ok(d, G) && G <= (int)tunable("batch_scatter_max_g", BATCH_SCATTER_MAX_G_DEFAULT) ? SWEEP_BATCH_MAX : 1;
 }
+// the largest group sp_process_queries_sharded_batched takes on this shard: 16 / 8 on a planar row shard (its two-tile rule), 8 elsewhere
+extern "C" int sp_shard_group_max_(const sp_db_t* db) {
+  return db && db->planar_resident && db->num_shards > 1 ? planar_resident_group_max(db->nj) : SWEEP_BATCH_MAX;
+}
+extern "C" int sp_db_num_shards_(const sp_db_t* db) { return db ? db->num_shards : 0; }
 void sp_set_last_error_(const char* msg) { g_last_error = msg ? msg : ""; }
 void sp_note_path_(uint64_t bits) { note_path(bits); }
 
@@ -862,6 +904,42 @@ sp_db_t* sp_db_create_planar(const sp_params_t* h) {
     return d;
   });
 }
+// Row shard `shard` of `num_shards` whose only resident form is the digit-planar layout, columns in the order of the exchange
+// (planar_resident.hpp): what the sharded flows read with the 1 .. 16-query scatter pass (k_sweep_planar_scatter).
+sp_db_t* sp_db_create_planar_shard(const sp_params_t* h, int shard, int num_shards) {
+  return guarded_handle([&] {
+    need(h != nullptr, "params is null");
+    const Params& p = h->p;
+    need(num_shards != 1, "sp_db_create_planar_shard: one shard is the whole database: use sp_db_create_planar");
+    need((num_shards == 2 || num_shards == 4 || num_shards == 8) && shard >= 0 && shard < num_shards,
+         "sp_db_create_planar_shard: num_shards must be 2, 4 or 8 and 0 <= shard < num_shards");
+    need(p.dim0() % (size_t)num_shards == 0, "dim0 not divisible by num_shards");
+    const size_t nj = p.dim0() / (size_t)num_shards;
+    if (!planar_resident_shape_ok((int)std::min<size_t>(p.num_per(), 1u << 30), (int)std::min<size_t>(nj, 1u << 30)) ||
+        p.num_per() / (size_t)num_shards < 2)
+      throw ArgError("sp_db_create_planar_shard: the digit-planar layout needs (dim0 / num_shards) % 64 == 0, dim0 / num_shards <= 512 and "
+                     "num_per % 128 == 0 (dim0 / num_shards = " + std::to_string(nj) + ", num_per = " + std::to_string(p.num_per()) + ")");
+    need(tunable("batch_planar", 1) != 0 && tunable("batch_mfma", 1) != 0,
+         "sp_db_create_planar_shard: the switches batch_planar and batch_mfma must be on when a planar-resident database is created");
+    auto d = std::make_unique<sp_db>();
+    d->params = h;
+    HIP_CHECK(hipGetDevice(&d->device));
+    d->planar_resident = true;
+    d->planar_state = -1;   // no copy beside the words, ever
+    d->packed = 0;
+    d->shard = shard;
+    d->num_shards = num_shards;
+    d->nj = (int)nj;
+    d->j0 = shard * d->nj;
+    d->np_local = (int)p.num_per();
+    const size_t bytes = sweep_planar_bytes((int)p.planes(), d->np_local, d->nj);   // a multiple of 8
+    d->words.alloc_streaming(bytes / 8, tunable("db_contiguous", 0) != 0);   // throws OomError
+    HIP_CHECK(hipMemset(d->words.p, 0x80, bytes));
+    HIP_CHECK(hipDeviceSynchronize());
+    const_cast<sp_params*>(h)->device_state();
+    return d;
+  });
+}
 const char* sp_db_format(const sp_db_t* d) {
   if (!d) return "";
   return d->sparse ? "sparse" : d->planar_resident ? "planar" : d->packed ? "packed" : "words8";
@@ -899,7 +977,7 @@ int sp_db_load_plane(sp_db_t* d, int plane, int z0, int nz, const uint64_t* word
       const int cnt = std::min(zs, nz - z);
       h2d_sync(d->upload.p, words + (size_t)z * row_words, (size_t)cnt * row_words * 8);
       if (d->planar_resident)   // the window of z-rows straight to planar entries
-        launch_planar_from_ref(planar_words(*d), stage, plane, z0 + z, cnt, d->np_local, d->nj, 0);
+        launch_planar_from_ref(planar_words(*d), stage, plane, z0 + z, cnt, d->np_local, d->nj, planar_shape(*d), 0);
       else
         launch_db_relayout(d->words.p, plane, stage, z0 + z, cnt, d->np_local, (int)p.dim0(), d->j0, d->nj,
                            d->packed, d->colmap(), 0);
@@ -951,7 +1029,7 @@ int sp_db_load_items(sp_db_t* d, const uint8_t* file, size_t file_len) {
       d->upload.ensure(raw + chunks * POLY_LEN * 16 * (size_t)ncols * 8);
       u64* stage = reinterpret_cast<u64*>(d->upload.p + raw);
       for (int jg = 0; jg < d->nj / 16; jg++) {
-        const size_t item0 = (size_t)16 * jg * p.num_per();
+        const size_t item0 = (size_t)(d->j0 + 16 * jg) * p.num_per();   // (a row shard: the file's rows j0 ..)
         const size_t off = item0 * p.db_item_size;
         const size_t have = off < file_len ? std::min(16 * row_bytes + tail, file_len - off) : 0;
         if (have) h2d_sync(d->upload.p, file + off, have);
@@ -961,7 +1039,7 @@ int sp_db_load_items(sp_db_t* d, const uint8_t* file, size_t file_len) {
           e.packed = 0;
           e.num_per = ncols;
           e.cm = ColMap{ii0, 1, d->np_local};
-          e.j0 = 16 * jg;
+          e.j0 = d->j0 + 16 * jg;
           e.nj = 16;
           e.win = d->upload.p;
           e.win_item0 = item0;
@@ -970,7 +1048,7 @@ int sp_db_load_items(sp_db_t* d, const uint8_t* file, size_t file_len) {
           e.jp0 = 0;
           e.njp = 8;
           launch_db_encode(D.T, e, 0);
-          launch_planar_from_stage(planar_words(*d), stage, (int)chunks, jg, ii0, ncols, d->np_local, d->nj, 0);
+          launch_planar_from_stage(planar_words(*d), stage, (int)chunks, jg, ii0, ncols, d->np_local, d->nj, planar_shape(*d), 0);
         }
         HIP_CHECK(hipDeviceSynchronize());
       }
@@ -1134,7 +1212,7 @@ int sp_db_fill_synthetic(sp_db_t* d, uint64_t seed) {
     sp_db::WriteScope write(*d);
     const Params& p = d->params->p;
     if (d->planar_resident)
-      launch_planar_synth(planar_words(*d), seed, (int)p.planes(), d->np_local, d->nj, 0);
+      launch_planar_synth(planar_words(*d), seed, (int)p.planes(), d->np_local, d->nj, planar_shape(*d), 0);
     else
       launch_db_synth(d->words.p, seed, (int)p.planes(), d->np_local, (int)p.dim0(), d->j0, d->nj, d->packed, d->colmap(), 0);
     HIP_CHECK(hipDeviceSynchronize());
@@ -1166,7 +1244,8 @@ int sp_db_read_ref(const sp_db_t* d, int plane, int z, int ii, int j0, int count
     check_device(d->device);
     DevBuf<u64> tmp((size_t)std::max(count, 1));
     if (d->planar_resident)
-      launch_planar_read(tmp.p, reinterpret_cast<const unsigned char*>(d->words.p), plane, z, ii, j0, count, d->np_local, d->nj, 0);
+      launch_planar_read(tmp.p, reinterpret_cast<const unsigned char*>(d->words.p), plane, z, ii, j0, count, d->np_local, d->nj,
+                         planar_shape(*d), 0);
     else
       launch_db_read(tmp.p, d->words.p, plane, z, ii / d->col_G, j0, count, d->np_local, d->nj, d->packed, 0);
     HIP_CHECK(hipMemcpy(out, tmp.p, (size_t)count * 8, hipMemcpyDeviceToHost));
@@ -1295,6 +1374,8 @@ int sp_query_sweep(sp_query_t* q, const sp_db_t* db) {
       run_sweep_sparse(W, *db, q->sparse_index->col_ptr.p, q->sparse_index->col_rows.p, q->sparse_index->col_slots.p);
       W.zero_shortcuts = true;
     } else if (db->planar_resident) {
+      // a planar row shard keeps its columns in the exchange's order and has the scatter-form pass only: no plain partial
+      need(db->num_shards == 1, "sp_query_sweep does not take a planar row shard (sp_db_create_planar_shard): use sp_query_sweep_scatter*");
       // a group of one: the one-tile pass on the query's own stream (the VALU and ring kernels never see this handle)
       W.ensure_sweep();
       sp_query_t* one[1] = {q};
@@ -1313,7 +1394,7 @@ int sp_query_sweep(sp_query_t* q, const sp_db_t* db) {
 int sp_query_sweep_scatter(sp_query_t* q, const sp_db_t* db, int G) {
   return guarded([&] {
     need(q && db, "null argument");
-    refuse_planar_resident(db, "sp_query_sweep_scatter");
+    refuse_planar_unsharded(db, "sp_query_sweep_scatter");
     need(q->state == 1, "sp_query_sweep_scatter: query not in 'begun' state");
     need(db->params == q->params, "db was created for different params");
     need_rows_of(q, db);
@@ -1324,6 +1405,9 @@ int sp_query_sweep_scatter(sp_query_t* q, const sp_db_t* db, int G) {
     Workspace& W = *q->ws;
     if (db->sparse) {   // chunk-major: chunk g = [plane][r][crt][z][ii / G]
       sweep_sparse_scatter(q, db, G, 0, (int)q->params->p.planes(), false);
+    } else if (db->planar_resident) {   // a group of one, the same chunk-major layout
+      sp_query_t* one[1] = {q};
+      planar_shard_pass(one, 1, db, G, 0, (int)q->params->p.planes(), true);
     } else {
       ScatterLayout scatter(W, G);
       run_sweep(W, *db);
@@ -1336,7 +1420,7 @@ int sp_query_sweep_scatter(sp_query_t* q, const sp_db_t* db, int G) {
 int sp_query_sweep_scatter_plane(sp_query_t* q, const sp_db_t* db, int G, int plane) {
   return guarded([&] {
     need(q && db, "null argument");
-    refuse_planar_resident(db, "sp_query_sweep_scatter_plane");
+    refuse_planar_unsharded(db, "sp_query_sweep_scatter_plane");
     need(db->params == q->params, "db was created for different params");
     need_rows_of(q, db);
     const Params& p = q->params->p;
@@ -1350,6 +1434,9 @@ int sp_query_sweep_scatter_plane(sp_query_t* q, const sp_db_t* db, int G, int pl
     W.ensure_sweep();
     if (db->sparse) {
       sweep_sparse_scatter(q, db, G, plane, 1, true);
+    } else if (db->planar_resident) {   // a group of one: this plane's z-range
+      sp_query_t* one[1] = {q};
+      planar_shard_pass(one, 1, db, G, plane, 1, false);
     } else {
       ScatterLayout scatter(W, G);
       launch_plane_sweep(W, *db, (size_t)plane);
@@ -1395,6 +1482,10 @@ int sp_query_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t
           HIP_CHECK(hipEventRecord(qs[i]->ws->ev[2], qs[i]->ws->stream));
         }
       }
+    } else if (db->planar_resident) {
+      // a planar row shard: one pass (k_sweep_planar_scatter) for every group size, one query tile or two
+      planar_shard_pass(qs, batch, db, G, 0, (int)planes, false);
+      for (int i = 0; i < batch; i++) group_pass_done(qs, i);
     } else if (scatter_group_desc(qs, batch, db, G, d)) {
       // ordered after every query's expansion (ev[1], recorded by sp_query_begin_for_db) ...
       Workspace& W0 = group_pass_stream(qs, batch);

@@ -426,7 +426,8 @@ extern "C" int sp_process_query_batch(const sp_params_t* h, const sp_pp_t* const
   const BatchArgs a{h, pps, queries, query_lens, batch, db, out, out_stride, out_len, std::chrono::steady_clock::now()};
   const bool batched = db->packed && db->num_shards == 1 && db->col_G == 1 && !tunable("no_batch_sweep", 0);
   if (db->sparse) return answer_sparse(a);
-  if (db->planar_resident) return answer_in_groups(a);   // lists of any length: groups of up to 16, whatever the switches say now
+  // lists of any length: groups of up to 16, whatever the switches say now (a planar row shard is refused per query, as any shard)
+  if (db->planar_resident && db->num_shards == 1) return answer_in_groups(a);
   if (batched) return answer_in_groups(a);
   const bool narrow = !db->packed && db->num_shards == 1 && db->col_G == 1 && !tunable("no_batch_sweep", 0);
   return narrow ? answer_narrow(a) : answer_in_flight(a);

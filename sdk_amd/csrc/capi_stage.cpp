@@ -115,7 +115,8 @@ int sp_bench_sweep_batch(sp_query_t* const* qs, int batch, const sp_db_t* db, in
     // ... or an unsharded narrow one (8-byte words, 2 <= num_per <= 64) for 2 .. 8 queries: the group's one pass, k_sweep_narrow_batch
     // (a single query is never a group there: it is refused as on every other 8-byte database)
     const bool narrow = !db->packed && db->num_shards == 1 && db->col_G == 1 && batch >= 2 && sweep_narrow_batch_shape_ok(db->np_local, db->nj);
-    need(narrow || db->planar_resident || (db->packed && db->num_shards == 1 && db->col_G == 1), "the batched pass needs an unsharded PACKED database");
+    need(narrow || (db->planar_resident && db->num_shards == 1) || (db->packed && db->num_shards == 1 && db->col_G == 1),
+         "the batched pass needs an unsharded PACKED database");
     check_device(db->device);
     for (int i = 0; i < batch; i++) {
       need(qs[i] && qs[i]->state >= 1, "query not begun");
@@ -163,6 +164,19 @@ int sp_bench_sweep_scatter_group(sp_query_t* const* qs, int batch, const sp_db_t
           run_sweep_sparse_scatter_group(Ws, batch, *db, idx.col_ptr.p, idx.col_rows.p, idx.col_slots.p, G, W0.stream);
         else
           run_sweep_sparse_group(Ws, batch, *db, idx.col_ptr.p, idx.col_rows.p, idx.col_slots.p, W0.stream);
+      });
+      return;
+    }
+    if (db->planar_resident) {   // a planar row shard: k_sweep_planar_scatter, every plane, per-plane layout (there is no plain form)
+      need(layout == 1, "a planar row shard has the scatter-form pass only (layout 1)");
+      for (int i = 0; i < batch; i++) qs[i]->ws->ensure_sweep();
+      PlanarPin none;
+      SweepBatchDesc pd = group_pass(*db, qs, batch, false, none);
+      Workspace& Wp = *qs[0]->ws;
+      const int planes = (int)db->params->p.planes();
+      *ms_per_pass = timed_reps(Wp.stream, iters, [&] {
+        sweep_planar_resident_prepare(Wp.D->T, pd, Wp.stream);
+        launch_sweep_planar_scatter(Wp.D->T, pd, G, 0, planes, false, Wp.stream);
       });
       return;
     }

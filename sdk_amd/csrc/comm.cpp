@@ -33,6 +33,8 @@ extern "C" void sp_set_last_error_(const char* msg);  // capi.cpp
 extern "C" void sp_note_path_(uint64_t bits);         // capi.cpp
 extern "C" void sp_shard_split_hint_(int on);         // capi.cpp: may the next sp_query_begin_for_db of this thread split the expansion?
 extern "C" int sp_scatter_group_choice_(const sp_db_t* shard, int G);   // capi.cpp: group size of a batched sharded list left to the library
+extern "C" int sp_shard_group_max_(const sp_db_t* shard);               // capi.cpp: largest group of a batched list on this shard (8, or 16 / 8 on a planar row shard)
+extern "C" int sp_db_num_shards_(const sp_db_t* db);                    // capi.cpp
 
 namespace {
 
@@ -49,11 +51,17 @@ void hip_ok(hipError_t e, const char* what) {
 void nccl_ok(ncclResult_t r, const char* what) {
   if (r != ncclSuccess) throw Fail{SP_E_HIP, std::string(what) + ": " + ncclGetErrorString(r)};
 }
-// a planar-resident database (sp_db_create_planar) is never a shard: the sharded flows sweep PACKED or 8-byte words per plane
-bool refuse_planar(const sp_db_t* shard, const char* what) {
+// an unsharded planar-resident database (sp_db_create_planar) is never a shard, not even of one rank: the sharded flows take PACKED or
+// 8-byte shards and planar ROW SHARDS (sp_db_create_planar_shard) -- of as many shards as the communicator has ranks, checked here so
+// that a wrong handle enqueues nothing and enters no collective
+bool refuse_planar(const sp_db_t* shard, const char* what, int world) {
   if (std::strcmp(sp_db_format(shard), "planar") != 0) return false;
-  sp_set_last_error_((std::string(what) + " does not take a planar-resident database (sp_db_create_planar): sharded flows need PACKED or 8-byte shards").c_str());
-  return true;
+  const int S = sp_db_num_shards_(shard);
+  if (S == 1)
+    sp_set_last_error_((std::string(what) + " does not take a planar-resident database (sp_db_create_planar): sharded flows need PACKED, 8-byte or planar row shards (sp_db_create_planar_shard)").c_str());
+  else if (S != world)
+    sp_set_last_error_((std::string(what) + ": the planar row shard is one of " + std::to_string(S) + ", the communicator has " + std::to_string(world) + " ranks").c_str());
+  return S == 1 || S != world;
 }
 void sp_ok(int rc, const char* what) {
   if (rc != SP_OK) throw Fail{rc, std::string(what) + ": " + sp_last_error()};
@@ -268,6 +276,22 @@ int sp_comm_reserve_batch(sp_comm_t* c, const sp_params_t* h, int group) {
   return guarded_comm([&] { comm_reserve(c, h, group == 0 ? 8 : group); });
 }
 
+// sp_comm_reserve_batch for a given shard: up to the largest group a batched list takes on it (16 on a planar row shard whose shape takes
+// two query tiles); group = 0 = that largest group
+int sp_comm_reserve_batch_for(sp_comm_t* c, const sp_params_t* h, const sp_db_t* shard, int group) {
+  if (!c || !h || !shard) {
+    sp_set_last_error_("null argument");
+    return SP_E_ARG;
+  }
+  const int group_max = sp_shard_group_max_(shard);
+  if (group < 0 || group > group_max) {
+    sp_set_last_error_(("group must be 0 (= " + std::to_string(group_max) + ") or 1 .. " + std::to_string(group_max) + " on this shard").c_str());
+    return SP_E_ARG;
+  }
+  std::lock_guard<std::mutex> lk(c->mu);
+  return guarded_comm([&] { comm_reserve(c, h, group == 0 ? group_max : group); });
+}
+
 namespace {
 // One sharded query as three enqueue stages, so that a list of queries can be software-pipelined: while query k's planes are
 // swept, query k + 1 is already expanding on its own streams.
@@ -367,7 +391,7 @@ int sp_process_query_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t* 
     sp_set_last_error_("null argument");
     return SP_E_ARG;
   }
-  if (refuse_planar(shard, "sp_process_query_sharded")) return SP_E_ARG;
+  if (refuse_planar(shard, "sp_process_query_sharded", c->world)) return SP_E_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   ShardedRun r;
   int rc = guarded_comm([&] {
@@ -434,13 +458,13 @@ int sp_process_queries_sharded(sp_comm_t* c, const sp_params_t* h, const sp_pp_t
     sp_set_last_error_("null argument");
     return SP_E_ARG;
   }
-  if (refuse_planar(shard, "sp_process_queries_sharded")) return SP_E_ARG;
+  if (refuse_planar(shard, "sp_process_queries_sharded", c->world)) return SP_E_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   return queries_sharded_locked(c, h, pps, queries, query_lens, n, shard, out, out_stride, out_len);
 }
 
-// ---- the same list with the database pass shared inside groups of up to 8 queries ---------------------------------------------
-// Order of the collectives, a function of (n, group, params) alone -- every rank passes the same list, so every rank issues
+// ---- the same list with the database pass shared inside groups of up to 8 queries (up to 16 on a planar row shard) ---------------
+// Order of the collectives, a function of (n, group, params, the shard's shape) alone -- every rank passes the same list, so every rank issues
 // the same sequence on its exchange stream.  For each group of B = min(group, n - first) queries, in list order:
 //   for i in 0 .. B:  for plane in 0 .. planes:  reduce_scatter_u32(query i's plane region -> region i of the receive buffer)
 //   for i in 0 .. B:  all_gather_u64(query i's local ciphertexts -> region i of the gather buffer)
@@ -456,9 +480,9 @@ int sp_process_queries_sharded_batched(sp_comm_t* c, const sp_params_t* h, const
     sp_set_last_error_("null argument");
     return SP_E_ARG;
   }
-  if (refuse_planar(shard, "sp_process_queries_sharded_batched")) return SP_E_ARG;
-  if (group < 0 || group > 8) {
-    sp_set_last_error_("group must be 0 (the library's choice) or 1 .. 8");
+  if (refuse_planar(shard, "sp_process_queries_sharded_batched", c->world)) return SP_E_ARG;
+  if (group < 0 || group > sp_shard_group_max_(shard)) {
+    sp_set_last_error_("group must be 0 (the library's choice) or 1 .. 8 (1 .. 16 on a planar row shard whose shape takes two query tiles)");
     return SP_E_ARG;
   }
   // every query's length before anything is begun: a bad list must not leave this rank inside a collective the others never enter
@@ -470,7 +494,8 @@ int sp_process_queries_sharded_batched(sp_comm_t* c, const sp_params_t* h, const
     }
   std::lock_guard<std::mutex> lk(c->mu);
   const int G = c->world;
-  if (group == 0) group = sp_scatter_group_choice_(shard, G);   // 8 where the scatter-form pass takes this shard (and pays), else 1
+  // 8 where the scatter-form pass takes this shard (and pays), 16 / 8 on a planar row shard (its two-tile rule), else 1
+  if (group == 0) group = sp_scatter_group_choice_(shard, G);
   if (group == 1 || n == 0) return queries_sharded_locked(c, h, pps, queries, query_lens, n, shard, out, out_stride, out_len);
   std::vector<ShardedRun> cur, nxt;
   auto drop = [&](std::vector<ShardedRun>& v) {
@@ -495,7 +520,7 @@ int sp_process_queries_sharded_batched(sp_comm_t* c, const sp_params_t* h, const
     for (int first = 0; first < n; first += group) {
       const int B = (int)cur.size();
       const size_t planes = cur[0].planes, local_words = cur[0].local_words;
-      sp_query_t* qs[8];
+      sp_query_t* qs[16];
       for (int i = 0; i < B; i++) qs[i] = cur[i].q;
       sp_ok(sp_query_sweep_scatter_group(qs, B, shard, G), "sp_query_sweep_scatter_group");
       const size_t words = sp_query_partial_words(qs[0]), pw = words / planes, chunk = pw / (size_t)G;

@@ -461,19 +461,33 @@ int planar_resident_group_max(int nj);
 // sp_synth_word(seed, reference index); the 16-row group jg of columns ii0 .. ii0 + ncols - 1 from the 8-byte words
 // stage[plane][z][16][ncols] k_db_encode wrote; `n_items` single items from the 8-byte words k_db_encode_quads wrote as a database of
 // two rows and np_s columns (item r = entry r & 3 of quad r >> 2; cells[r] = its local row and column, an item listed once)
-void launch_planar_from_ref(unsigned char* planar, const u64* src, int plane, int z0, int nz, int num_per, int nj, hipStream_t s);
-void launch_planar_synth(unsigned char* planar, u64 seed, int planes, int num_per, int nj, hipStream_t s);
+// `sh`: the handle as a row shard (sp_db_create_planar_shard) -- src / the synthetic index have dim0 rows of which the handle holds
+// j0 .. j0 + nj - 1, and reference column ii lives at resident column (ii % G) * (num_per / G) + ii / G; {} = unsharded.  Columns handed
+// to these functions (ii0, cells, ii) are reference columns, rows (jg, cells, jl0) local ones.
+struct PlanarShardShape {
+  int dim0 = 0;   // rows of the reference (0: nj)
+  int j0 = 0;
+  int G = 1;
+};
+void launch_planar_from_ref(unsigned char* planar, const u64* src, int plane, int z0, int nz, int num_per, int nj, PlanarShardShape sh,
+                            hipStream_t s);
+void launch_planar_synth(unsigned char* planar, u64 seed, int planes, int num_per, int nj, PlanarShardShape sh, hipStream_t s);
 void launch_planar_from_stage(unsigned char* planar, const u64* stage, int planes, int jg, int ii0, int ncols, int num_per, int nj,
-                              hipStream_t s);
+                              PlanarShardShape sh, hipStream_t s);
 void launch_planar_put_items(unsigned char* planar, const u64* stage, int planes, size_t np_s, const PlanarPatchCell* cells, size_t n_items,
-                             int num_per, int nj, hipStream_t s);
+                             int num_per, int nj, PlanarShardShape sh, hipStream_t s);
 // canonical words (plane, z, ii, rows jl0 .. + count) gathered back from their digit bytes into out[count] (device)
 void launch_planar_read(u64* out, const unsigned char* planar, int plane, int z, int ii, int jl0, int count, int num_per, int nj,
-                        hipStream_t s);
+                        PlanarShardShape sh, hipStream_t s);
 // a group of 1 .. 16 queries over such a database (d.planar = its words, d.rq = sweep_batch_rq_words(nj, tiles) words of scratch): the
 // query tables, then the pass -- k_sweep_planar with one query tile for 1 .. 8 queries, launch_sweep_planar for 9 .. 16
 void sweep_planar_resident_prepare(const DevTables& T, SweepBatchDesc& d, hipStream_t s);
 void launch_sweep_planar_resident(const DevTables& T, const SweepBatchDesc& d, hipStream_t s);
+// The same pass over a planar ROW SHARD of G (k_sweep_planar_scatter): d.planar = the shard's words of plane `plane0`, d.planes = planes
+// swept, d.out[b] = query b's partial buffer, written in the per-plane reduce-scatter layout [plane][ii % G][r][crt][z][ii / G] from plane
+// plane0 on, or (all_planes, plane0 = 0) in sp_query_sweep_scatter's [ii % G][plane][r][crt][z][ii / G].  Prepared as above.
+void launch_sweep_planar_scatter(const DevTables& T, const SweepBatchDesc& d, int G, int plane0, int total_planes, bool all_planes,
+                                 hipStream_t s);
 // does this shape / group size run on the matrix cores (switch batch_mfma, default on from batch_mfma_min = 4 queries)?
 // Groups of more than SWEEP_BATCH_MAX queries exist only there.
 bool sweep_batch_wants_mfma(const SweepBatchDesc& d);

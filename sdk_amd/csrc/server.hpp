@@ -224,8 +224,11 @@ struct sp_db {
   // sp_db_create_planar: `words` IS the digit-planar layout (sweep_planar.hpp; planar_resident.hpp writes it), 8 bytes per word and
   // the handle's only resident form: packed = 0, planar_state = -1 and `planar` stays empty for the handle's life, so ensure_planar,
   // drop_planar, WriteScope and the out-of-memory ladder of the list flow find nothing to build or to give back.  Every query, alone
-  // or in a list, goes through the group flow (k_sweep_planar with one or two query tiles); the per-plane sweeps, the scatter forms
-  // and shards do not exist for it.  Decided from the switches when the handle is created, never looked at again.
+  // or in a list, goes through the group flow (k_sweep_planar with one or two query tiles); the per-plane sweeps and the scatter forms
+  // do not exist for it.  Decided from the switches when the handle is created, never looked at again.
+  // sp_db_create_planar_shard: the same with num_shards = 2 / 4 / 8 -- the shard's rows j0 .. j0 + nj - 1, the columns in the order of the
+  // exchange (planar_resident.hpp).  It is read by the scatter sweeps only (k_sweep_planar_scatter, groups of 1 .. 16): the plain group
+  // flow and sp_query_sweep refuse it.
   bool planar_resident = false;
   std::mutex mu;
   // a bulk write of `words`: holds `mu` and, on every path out (after the last write has completed), drops the planar copy

@@ -256,37 +256,47 @@ int planar_resident_group_max(int nj) {
   }
   return (size_t)lds_optin >= (size_t)nj * 256 ? SWEEP_GROUP_MAX : SWEEP_BATCH_MAX;
 }
-void launch_planar_from_ref(unsigned char* planar, const u64* src, int plane, int z0, int nz, int num_per, int nj, hipStream_t s) {
+// a handle's row window and column order as the kernels take them (an unsharded handle: every row, the identity)
+static PlanarRows planar_rows(const PlanarShardShape& sh, int nj) { return PlanarRows{sh.dim0 > 0 ? sh.dim0 : nj, sh.j0}; }
+static PlanarCols planar_cols(const PlanarShardShape& sh, int num_per) {
+  int lgG = 0, lgn = 0;
+  while ((1 << lgG) < sh.G) lgG++;
+  while ((1 << lgn) < num_per) lgn++;
+  return PlanarCols{lgG, lgn - lgG};
+}
+void launch_planar_from_ref(unsigned char* planar, const u64* src, int plane, int z0, int nz, int num_per, int nj, PlanarShardShape sh,
+                            hipStream_t s) {
   if (nz <= 0) return;
   const size_t threads = (size_t)nz * (size_t)num_per * (size_t)(nj >> 4);
   hipLaunchKernelGGL(k_planar_from_ref, dim3((unsigned)std::min<size_t>((threads + 255) / 256, 256 * 64)), dim3(256), 0, s, planar, src,
-                     (size_t)plane * N + (size_t)z0, nz, num_per, nj);
+                     (size_t)plane * N + (size_t)z0, nz, num_per, nj, planar_rows(sh, nj), planar_cols(sh, num_per));
   launched(0, "k_planar_from_ref");
 }
-void launch_planar_synth(unsigned char* planar, u64 seed, int planes, int num_per, int nj, hipStream_t s) {
-  hipLaunchKernelGGL(k_planar_synth, dim3(256 * 64), dim3(256), 0, s, planar, seed, (size_t)planes * N, num_per, nj);
+void launch_planar_synth(unsigned char* planar, u64 seed, int planes, int num_per, int nj, PlanarShardShape sh, hipStream_t s) {
+  hipLaunchKernelGGL(k_planar_synth, dim3(256 * 64), dim3(256), 0, s, planar, seed, (size_t)planes * N, num_per, nj, planar_rows(sh, nj),
+                     planar_cols(sh, num_per));
   launched(0, "k_planar_synth");
 }
 void launch_planar_from_stage(unsigned char* planar, const u64* stage, int planes, int jg, int ii0, int ncols, int num_per, int nj,
-                              hipStream_t s) {
+                              PlanarShardShape sh, hipStream_t s) {
   const size_t threads = (size_t)planes * N * (size_t)ncols;
   hipLaunchKernelGGL(k_planar_from_stage, dim3((unsigned)std::min<size_t>((threads + 255) / 256, 256 * 64)), dim3(256), 0, s, planar, stage,
-                     (size_t)planes * N, jg, ii0, ncols, num_per, nj);
+                     (size_t)planes * N, jg, ii0, ncols, num_per, nj, planar_cols(sh, num_per));
   launched(0, "k_planar_from_stage");
 }
 void launch_planar_put_items(unsigned char* planar, const u64* stage, int planes, size_t np_s, const PlanarPatchCell* cells, size_t n_items,
-                             int num_per, int nj, hipStream_t s) {
+                             int num_per, int nj, PlanarShardShape sh, hipStream_t s) {
   if (n_items == 0) return;
   const size_t zps = (size_t)planes * N;   // (n_items * planes * N / 256 blocks: the caller's windows keep n_items * planes <= 2^23)
   hipLaunchKernelGGL(k_planar_put_items, dim3((unsigned)((n_items * zps + 255) / 256)), dim3(256), 0, s, planar, stage, zps, np_s, cells,
-                     n_items, num_per, nj);
+                     n_items, num_per, nj, planar_cols(sh, num_per));
   launched(0, "k_planar_put_items");
 }
 void launch_planar_read(u64* out, const unsigned char* planar, int plane, int z, int ii, int jl0, int count, int num_per, int nj,
-                        hipStream_t s) {
+                        PlanarShardShape sh, hipStream_t s) {
   if (count <= 0) return;
   hipLaunchKernelGGL(k_planar_read, dim3((count + 63) / 64), dim3(64), 0, s, out, planar, (size_t)plane * N + (size_t)z, ii, jl0, count,
-                     num_per, nj);
+                     num_per, nj, planar_cols(sh, num_per));
   launched(0, "k_planar_read");
 }
 // The group's query tables for a pass over a planar-resident database (d.planar = its words): one tile's planar tables and offset
@@ -358,6 +368,67 @@ void launch_sweep_planar_resident(const DevTables& T, const SweepBatchDesc& d, h
   if (eight && ring4) SP_PLANAR1(4, 8) else if (eight) SP_PLANAR1(2, 8) else if (ring4) SP_PLANAR1(4, 4) else SP_PLANAR1(2, 4)
 #undef SP_PLANAR1
   launched(PATH_SWEEP_BATCH | PATH_SWEEP_MFMA | PATH_SWEEP_PLANAR, "k_sweep_planar (one query tile)");
+}
+
+// ---- the pass over a planar ROW SHARD (sp_db_create_planar_shard), in the reduce-scatter layout ------------------------------------
+// k_sweep_planar's scatter form: one query tile for 1 .. 8 queries, two for 9 .. 16; workgroup shape and ring depth by the rules of the
+// plain form (64 local rows: two units per pass, so the ring of 2).  The shard's resident column order (planar_resident.hpp) makes the
+// stores the plain form's; only the addresses differ, and they come from the descriptor, so the per-plane layout of
+// sp_query_sweep_scatter_plane / _group and the all-planes layout of sp_query_sweep_scatter are one kernel.
+// Path bits: scatter_out with sweep_batch | sweep_batch_mfma | sweep_batch_planar (| sweep_batch_mfma_two_tiles), a combination no other
+// flow reports; sweep_batch_scatter stays the name of k_sweep_mfma_scatter's pass over a PACKED shard and is NOT set here.
+void launch_sweep_planar_scatter(const DevTables& T, const SweepBatchDesc& d, int G, int plane0, int total_planes, bool all_planes,
+                                 hipStream_t s) {
+  if (!d.planar || !d.rq || !d.use_mfma || d.batch < 1 || d.batch > SWEEP_GROUP_MAX || !(G == 2 || G == 4 || G == 8) ||
+      !planar_resident_shape_ok(d.num_per, d.nj) || d.num_per / G < 2 || plane0 < 0 || d.planes < 1 || plane0 + d.planes > total_planes ||
+      (all_planes && plane0 != 0))
+    throw HipError("internal: not a prepared group of a planar row shard");
+  const int tiles = sweep_batch_tiles(d.batch);
+  const int npg = d.num_per / G;
+  SweepPlanarDesc m{};
+  m.db = d.planar;
+  m.rq = reinterpret_cast<const unsigned char*>(d.rq);
+  m.rq_off = d.rq + (size_t)tiles * N * (d.nj >> 4) * 128 * 4;
+  m.plane_stride = all_planes ? (size_t)4 * N * npg : (size_t)4 * N * d.num_per;
+  m.class_stride = all_planes ? (size_t)total_planes * 4 * N * npg : (size_t)4 * N * npg;
+  for (m.lg_npg = 0; (1 << m.lg_npg) < npg; m.lg_npg++) {}
+  const size_t out0 = all_planes ? 0 : (size_t)plane0 * m.plane_stride;
+  for (int b = 0; b < SWEEP_MFMA_MAX; b++) m.out[b] = d.out[b < d.batch ? b : 0] + out0;   // (b >= batch: never stored to)
+  m.batch = d.batch;
+  m.planes = d.planes;
+  m.num_per = d.num_per;
+  m.nj = d.nj;
+  const int chunks = d.num_per >> 7;
+  int cpw = (int)tunable("batch_mfma_cpw", 16);
+  cpw = std::max(1, std::min(cpw, chunks));
+  while (chunks % cpw) cpw--;
+  m.cpw = cpw;
+  const u64 qs[2] = {MODULUS_0, MODULUS_1};
+  for (int c = 0; c < 2; c++) {
+    m.c4[c] = (u32)((1ull << 32) % qs[c]);
+    m.c5[c] = (u32)((1ull << 40) % qs[c]);
+    m.c6[c] = (u32)((1ull << 48) % qs[c]);
+  }
+  const dim3 grid((unsigned)((size_t)d.planes * N * (chunks / cpw)));
+  const size_t lds = (size_t)tiles * d.nj * 128;   // the tiles' query planes of one z-row
+  const bool eight = (cpw % 2) == 0;
+  const bool ring4 = ((2 * (d.nj >> 6)) % 4) == 0;
+#define SP_PLANAR_SC(NBUF_, QT_, MINWG_, WAVES_)                                                                               \
+  {                                                                                                                            \
+    if (lds > 65536)                                                                                                           \
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sweep_planar_scatter<NBUF_, QT_, MINWG_, WAVES_>),        \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                    \
+    hipLaunchKernelGGL((k_sweep_planar_scatter<NBUF_, QT_, MINWG_, WAVES_>), grid, dim3(64 * WAVES_), lds, s, T, m);            \
+  }
+  if (tiles == 2) {
+    if (eight && ring4) SP_PLANAR_SC(4, 2, 1, 8) else if (eight) SP_PLANAR_SC(2, 2, 1, 8) else if (ring4) SP_PLANAR_SC(4, 2, 1, 4) else SP_PLANAR_SC(2, 2, 1, 4)
+  } else {
+    if (eight && ring4) SP_PLANAR_SC(4, 1, PLANAR1_MINWG, 8) else if (eight) SP_PLANAR_SC(2, 1, PLANAR1_MINWG, 8)
+    else if (ring4) SP_PLANAR_SC(4, 1, PLANAR1_MINWG, 4) else SP_PLANAR_SC(2, 1, PLANAR1_MINWG, 4)
+  }
+#undef SP_PLANAR_SC
+  launched(PATH_SCATTER_OUT | PATH_SWEEP_BATCH | PATH_SWEEP_MFMA | PATH_SWEEP_PLANAR | (tiles == 2 ? PATH_SWEEP_MFMA2 : 0),
+           tiles == 2 ? "k_sweep_planar_scatter" : "k_sweep_planar_scatter (one query tile)");
 }
 
 }  // namespace spiral

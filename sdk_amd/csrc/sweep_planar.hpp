@@ -49,6 +49,14 @@ struct SweepPlanarDesc {
   int planes, num_per, nj;        // nj % 64 == 0, nj <= 512, num_per % 128 == 0
   int cpw;
   u32 c4[2], c5[2], c6[2];        // 2^32, 2^40, 2^48 mod q_crt
+  // scatter form only (k_sweep_planar_scatter, a planar row shard of G): out[b] = query b's partial buffer in a reduce-scatter
+  // layout.  Resident column c' belongs to rank class c' >> lg_npg at position c' & (num_per / G - 1) (planar_resident.hpp,
+  // planar_col); word (plane, class, rc = r * 2 + crt, z, position) is at
+  //     plane * plane_stride + class * class_stride + (rc * N + z) * (num_per / G) + position,
+  // which is the per-plane layout [plane][g][r][crt][z][ii / G] (plane_stride = 4 N num_per, class_stride = 4 N num_per / G) and
+  // the all-planes layout [g][plane][r][crt][z][ii / G] (plane_stride = 4 N num_per / G, class_stride = planes * that) alike.
+  size_t plane_stride, class_stride;   // u32 words
+  int lg_npg;                          // log2(num_per / G)
 };
 
 // query digit planes of one tile of <= 8 queries: byte t of entry (z, block, c, b, lane = 16 kb + m) = signed digit b of residue c
@@ -155,8 +163,11 @@ static __global__ __launch_bounds__(256) void k_query_offset_terms2(DevTables T,
 // WAVES = 4: one wave per SIMD and workgroup; WAVES = 8: the workgroup's chunks are split between two sets of four waves that
 // share the z-row's query planes in LDS -- two waves per SIMD (they cover each other's waits) where two four-wave workgroups
 // would need the 64 KiB per query tile twice.
-template <int NBUF, int QT, int DIAG = 0, int MINWG = 1, int WAVES = 4>
-__global__ __launch_bounds__(64 * WAVES, MINWG) void k_sweep_planar(DevTables T, SweepPlanarDesc d) {
+// SCATTER: the epilogue stores to the reduce-scatter layout of the descriptor (a planar row shard, whose resident column order makes a
+// 128-column chunk part of ONE rank's run: the same 8-byte stores in 128-byte runs as the plain form, other addresses); everything
+// before the epilogue is the same code.
+template <int NBUF, int QT, int DIAG, int WAVES, bool SCATTER>
+__device__ __forceinline__ void sweep_planar_body(const DevTables& T, const SweepPlanarDesc& d) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_pl[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -262,14 +273,20 @@ __global__ __launch_bounds__(64 * WAVES, MINWG) void k_sweep_planar(DevTables T,
     }
     // modulus c of this chunk is done: recombine the digit sums, reduce, store (register i = query column 4 kb + i, lane mp =
     // columns 32 g + 2 mp + e)
-    const size_t col = (size_t)z * d.num_per + (size_t)(chunk0 + ch) * 128 + 32 * g + 2 * mp;
+    const int rcol = (chunk0 + ch) * 128 + 32 * g + 2 * mp;   // resident column of e = 0; e = 1 is the next one
+    // scatter form: the pair shares a class (num_per / G is even) and a chunk never straddles one unless it spans whole classes
+    const int npg = 1 << d.lg_npg;
+    const size_t col = SCATTER ? (size_t)(rcol >> d.lg_npg) * d.class_stride + (size_t)z * npg + (size_t)(rcol & (npg - 1))
+                               : (size_t)z * d.num_per + (size_t)rcol;
+    const size_t rc_stride = SCATTER ? (size_t)N * npg : rcw;
+    const size_t pl_off = SCATTER ? (size_t)plane * d.plane_stride : (size_t)plane * 4 * rcw;
     const ModConst mc = c ? m1 : m0;
 #pragma unroll
     for (int qt = 0; qt < QT; qt++)
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         if (8 * qt + 2 * kb + (i >> 1) < d.batch) {
-          u32* ob = ((i >> 1) ? out_b1[qt] : out_b0[qt]) + ((size_t)plane * 4 + (i & 1) * 2 + c) * rcw + col;
+          u32* ob = ((i >> 1) ? out_b1[qt] : out_b0[qt]) + pl_off + (size_t)((i & 1) * 2 + c) * rc_stride + col;
           const u32 oc = c ? off1[qt][i] : off0[qt][i];
           const u32 v0 = combine_digit_sums(acc[qt][0][0][i], acc[qt][0][1][i], acc[qt][0][2][i], acc[qt][0][3][i],
                                             acc[qt][0][4][i], acc[qt][0][5][i], acc[qt][0][6][i], mc, d.c4[c], d.c5[c], d.c6[c], oc);
@@ -281,6 +298,15 @@ __global__ __launch_bounds__(64 * WAVES, MINWG) void k_sweep_planar(DevTables T,
       }
   }
 #undef SPL_LOAD
+}
+template <int NBUF, int QT, int DIAG = 0, int MINWG = 1, int WAVES = 4>
+__global__ __launch_bounds__(64 * WAVES, MINWG) void k_sweep_planar(DevTables T, SweepPlanarDesc d) {
+  sweep_planar_body<NBUF, QT, DIAG, WAVES, false>(T, d);
+}
+// the same pass over a planar ROW SHARD (sp_db_create_planar_shard), every query's output in its partial buffer's reduce-scatter layout
+template <int NBUF, int QT, int MINWG = 1, int WAVES = 4>
+__global__ __launch_bounds__(64 * WAVES, MINWG) void k_sweep_planar_scatter(DevTables T, SweepPlanarDesc d) {
+  sweep_planar_body<NBUF, QT, 0, WAVES, true>(T, d);
 }
 
 }  // namespace spiral

@@ -319,9 +319,17 @@ class Comm:
         from .spiral import _chk, lib
         _chk(lib().sp_comm_reserve_batch(C.c_void_p(self.h), C.c_void_p(params.h), C.c_int(group)))
 
+    def reserve_batch_for(self, params, shard, group=0):
+        """sp_comm_reserve_batch_for: reserve_batch for the groups a batched list takes on `shard` -- up to 16 on a planar row shard
+        (Database.planar_shard) whose shape allows two query tiles, up to 8 elsewhere; 0 = the shard's largest group"""
+        import ctypes as C
+        from .spiral import _chk, lib
+        _chk(lib().sp_comm_reserve_batch_for(C.c_void_p(self.h), C.c_void_p(params.h), C.c_void_p(shard.h), C.c_int(group)))
+
     def process_queries_batched(self, params, pps, queries, shard, group=0):
-        """sp_process_queries_sharded_batched: the list with ONE pass over the shard per group of up to 8 queries (group = 0:
-        the library's choice, 1 = the per-query flow of process_queries); the list of responses on rank 0, [] elsewhere"""
+        """sp_process_queries_sharded_batched: the list with ONE pass over the shard per group of up to 8 queries -- up to 16 on a
+        planar row shard (Database.planar_shard) -- (group = 0: the library's choice, 1 = the per-query flow of process_queries);
+        the list of responses on rank 0, [] elsewhere"""
         import ctypes as C
         from .spiral import _bytes, _chk, _p, lib, u8p
         n = len(queries)

@@ -416,13 +416,28 @@ class Database:
     def planar(cls, params, shard=0, num_shards=1):
         """A planar-resident database (sp_db_create_planar): the digit-planar layout the matrix-core group pass reads is its ONLY
         resident form (8 bytes per word, no second copy), read by every query of every list size -- for buckets where lists
-        dominate.  dim0 % 64 == 0, dim0 <= 512, num_per % 128 == 0; unsharded only (any other shard request raises)."""
+        dominate.  dim0 % 64 == 0, dim0 <= 512, num_per % 128 == 0; unsharded only (any other shard request raises: row shards of
+        this format are Database.planar_shard)."""
         if (shard, num_shards) != (0, 1):
             raise SpiralError("a planar-resident database is unsharded (sp_db_create_planar offers no shards)")
         self = cls.__new__(cls)
         self.params, self.shard, self.num_shards, self.by_columns = params, 0, 1, False
         lib().sp_db_create_planar.restype = C.c_void_p
         self.h = lib().sp_db_create_planar(_vp(params.h))
+        if not self.h:
+            raise SpiralError(_err())
+        return self
+
+    @classmethod
+    def planar_shard(cls, params, shard, num_shards):
+        """A planar ROW SHARD (sp_db_create_planar_shard): row shard `shard` of `num_shards` (2, 4 or 8) whose only resident form is
+        the digit-planar layout, columns in the order of the exchange.  Served through the sweep_scatter family and the Comm flows,
+        where a list takes up to 16 queries per pass over it.  dim0 / num_shards a multiple of 64 and <= 512, num_per % 128 == 0;
+        8 bytes per word instead of a PACKED shard's 7 -- for buckets where lists dominate."""
+        self = cls.__new__(cls)
+        self.params, self.shard, self.num_shards, self.by_columns = params, shard, num_shards, False
+        lib().sp_db_create_planar_shard.restype = C.c_void_p
+        self.h = lib().sp_db_create_planar_shard(_vp(params.h), C.c_int(shard), C.c_int(num_shards))
         if not self.h:
             raise SpiralError(_err())
         return self
@@ -573,8 +588,8 @@ class QueryRun:
 
     @staticmethod
     def sweep_scatter_group(runs, db, G):
-        """sp_query_sweep_scatter_group: ALL planes of the begun queries `runs` (1 .. 8, begun for row shard `db`) with one pass
-        over the shard; every run's partial buffer then holds what its own sweep_scatter_plane calls would have left"""
+        """sp_query_sweep_scatter_group: ALL planes of the begun queries `runs` (1 .. 8, on a planar row shard 1 .. 16; begun for row shard
+        `db`) with one pass over the shard; every run's partial buffer then holds what its own sweep_scatter_plane calls would have left"""
         arr = (C.c_void_p * len(runs))(*[r.h for r in runs])
         _chk(lib().sp_query_sweep_scatter_group(arr, C.c_int(len(runs)), _vp(db.h), C.c_int(G)))
         return runs
