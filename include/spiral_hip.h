@@ -207,6 +207,43 @@ int sp_db_prepare_batch(sp_db_t*, int* built);
 uint64_t sp_synth_word(uint64_t seed, uint64_t ref_index);
 /* Read back words of the reference-layout view (debug / tests): plane, z, ii, j0..j0+count within the shard's rows */
 int sp_db_read_ref(const sp_db_t*, int plane, int z, int ii, int j0, int count, uint64_t* out);
+/* Items back out of the resident words, on every format: the inverse of sp_db_load_items (server.rs:277-357 load_item_from_seek /
+ * load_db_from_seek) and of the upserts (lib/server/src/db/loading.rs:278-359), run on the device.  For item i = j * num_per + ii and
+ * chunk c = the plane index: the 2048 resident words at (plane c, z, ii, j) are inverse-transformed mod both primes (from_ntt,
+ * poly.rs:646-663), recenter_mod (server.rs:338-341) is undone -- with h = p / 2 a coefficient v <= h is x = v, v >= Q - (p - h - 1) is
+ * x = v - Q + p, anything else is not in the loader's image -- and the first W = ceil(nbytes * 8 / logp) coefficients are packed back,
+ * logp = ceil(log2 p) bits each, into the chunk's nbytes bytes [c * bpc, min((c + 1) * bpc, db_item_size)) of the item,
+ * bpc = ceil(db_item_size / chunks) (the inverse of read_arbitrary_bits, server.rs:312-315).  Coefficients from W on and bits past the
+ * chunk's bytes are ignored: where db_item_size is not a multiple of the chunk count, a file-loaded database holds the next item's
+ * spill there.
+ * out + k * db_item_size receives item item0 + k; present[k] (may be NULL) is 1 when this handle holds the item: a dense unsharded handle
+ * holds every item (all-zero ones included), a row shard the items of its rows, a column shard those of its columns, a sparse bucket
+ * or sparse shard the items in its store.  An item the handle does not hold reads as present 0 and db_item_size zero bytes.  Items
+ * speak reference coordinates on every format (a planar row shard's resident column order and a column shard's local columns included).
+ * A chunk polynomial with a coefficient z < W outside the loader's image is UNDECODABLE: it counts once in *undecodable (may be NULL; the
+ * count over the held items of the range), that coefficient reads as 0 and the call still returns SP_OK -- what a sp_db_fill_synthetic
+ * handle or arbitrary sp_db_load words yield.  count == 0: SP_OK, nothing written.  item0 + count > num_items or
+ * out_cap < count * db_item_size: SP_E_ARG, nothing enqueued, nothing written.
+ * Read-only: may run beside queries on the same handle and beside other readers, not beside the writers (the rule of
+ * sp_db_update_item).  The handle keeps one device-side READ buffer of its own (not counted by sp_db_device_bytes) from the first read on:
+ * at most db_load_window bytes (one item's words and bytes where that is smaller); a range is cut into windows of items, per window one
+ * gather launch (none on a sparse store), one decode launch and one copy out; nothing is allocated or freed between the kernels of a
+ * call (allocation rule).  Readers of one handle take turns at its buffer; they do not take the lock the lists hold. */
+int sp_db_read_items(const sp_db_t*, size_t item0, size_t count, uint8_t* out, size_t out_cap,
+                     uint8_t* present /* count bytes, may be NULL */, size_t* undecodable /* may be NULL */);
+/* count * (8 + db_item_size): a body_cap that always suffices for `count` items; no device call */
+size_t sp_db_export_rows_bound(const sp_db_t*, size_t count);
+/* The held items of the range as the body of POST /update-row (lib/server/src/db/loading.rs:361-377 update_many_items), one record per
+ * held item in index order: be32(4 + db_item_size) | be32(item index) | db_item_size item bytes.  sp_db_update_rows applies it to any
+ * handle of the same Params, so dst.update_rows(src.export_rows()) moves a live bucket to another format or shard count, and the body
+ * is a snapshot.  *body_len = bytes written, *records = their count (either may be NULL).  body_cap smaller than the records of the range:
+ * SP_E_ARG before any device work (the held items are known from the handle's shape and key map).  When at least one polynomial of the
+ * range is undecodable the call returns SP_E_STATE with *body_len = 0: an export that zeroes data silently is worse than none.
+ * The one inexact case: where db_item_size is not a multiple of the chunk count, a file-loaded source (sp_db_load_items) and its
+ * re-import agree on every item byte but not on the spill coefficients behind them (the records are zero padded, loading.rs:317-359) --
+ * their responses decode alike, the response bytes may differ.  Threading: as sp_db_read_items. */
+int sp_db_export_rows(const sp_db_t*, size_t item0, size_t count, uint8_t* body, size_t body_cap,
+                      size_t* body_len, size_t* records);
 size_t sp_db_device_bytes(const sp_db_t*);      /* the resident database words */
 size_t sp_db_batch_copy_bytes(const sp_db_t*);  /* the digit-planar copy beside them while it stands (sp_db_prepare_batch), else 0 */
 

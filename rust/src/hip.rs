@@ -92,6 +92,9 @@ pub mod sys {
         pub fn sp_db_batch_copy_bytes(db: *const sp_db_t) -> usize;
         pub fn sp_synth_word(seed: u64, ref_index: u64) -> u64;
         pub fn sp_db_read_ref(db: *const sp_db_t, plane: c_int, z: c_int, ii: c_int, j0: c_int, count: c_int, out: *mut u64) -> c_int;
+        pub fn sp_db_read_items(db: *const sp_db_t, item0: usize, count: usize, out: *mut u8, out_cap: usize, present: *mut u8, undecodable: *mut usize) -> c_int;
+        pub fn sp_db_export_rows_bound(db: *const sp_db_t, count: usize) -> usize;
+        pub fn sp_db_export_rows(db: *const sp_db_t, item0: usize, count: usize, body: *mut u8, body_cap: usize, body_len: *mut usize, records: *mut usize) -> c_int;
         pub fn sp_db_device_bytes(db: *const sp_db_t) -> usize;
         // ---- PublicParameters (client.rs:146-259)
         pub fn sp_pp_deserialize(p: *const sp_params_t, data: *const u8, len: usize) -> *mut sp_pp_t;
@@ -393,6 +396,27 @@ impl Database {
         let mut built: c_int = 0;
         must(check(unsafe { sys::sp_db_prepare_batch(self.0, &mut built) }));
         built != 0
+    }
+    /// Items `item0 .. item0 + count` back out of the resident words (`sp_db_read_items`, the inverse of `load_items` and the upserts):
+    /// `(count * item_size bytes, present flag per item, undecodable chunk polynomials)`.  An item this handle does not hold reads as
+    /// not present and zero bytes.  `item_size` is the params' `db_item_size`.
+    pub fn read_items(&self, item0: usize, count: usize, item_size: usize) -> Result<(Vec<u8>, Vec<bool>, usize), HipError> {
+        let mut out = vec![0u8; count * item_size];
+        let mut present = vec![0u8; count];
+        let mut undecodable = 0usize;
+        check(unsafe {
+            sys::sp_db_read_items(self.0, item0, count, out.as_mut_ptr(), out.len(), present.as_mut_ptr(), &mut undecodable)
+        })?;
+        Ok((out, present.into_iter().map(|b| b != 0).collect(), undecodable))
+    }
+    /// The held items of the range as one `/update-row` body (`sp_db_export_rows`): `dst.update_rows(&src.export_rows(0, n)?)` moves a
+    /// live bucket to another format or shard count.  `SP_E_STATE` when the range holds undecodable words.
+    pub fn export_rows(&self, item0: usize, count: usize) -> Result<Vec<u8>, HipError> {
+        let mut body = vec![0u8; unsafe { sys::sp_db_export_rows_bound(self.0, count) }];
+        let (mut len, mut records) = (0usize, 0usize);
+        check(unsafe { sys::sp_db_export_rows(self.0, item0, count, body.as_mut_ptr(), body.len(), &mut len, &mut records) })?;
+        body.truncate(len);
+        Ok(body)
     }
     pub fn device_bytes(&self) -> usize {
         unsafe { sys::sp_db_device_bytes(self.0) }

@@ -556,6 +556,32 @@ struct DbQuadRec {
 };
 void launch_db_encode_quads(const DevTables& T, const DbEncodeDesc& d, const DbQuadRec* quads, size_t n_quads, hipStream_t s);
 
+// ---- item read-back (sp_db_read_items; item_readback.hpp): the loaders above read backwards, a window of items at a time ----
+// Step 1, gather: the words of the handle's LOCAL items L0 .. L0 + nL - 1 (L = local row * np_local + local column: the held items of a
+// window of consecutive item indices are such a run in every dense form) -> dst[L - L0][plane][z], canonical lo | hi << 32.
+// db = the 8-byte words [plane][z][jl][il] or the PACKED unit stream ...
+void launch_items_gather(u64* dst, const u64* db, size_t L0, size_t nL, int np_local, int nj, int planes, int packed, hipStream_t s);
+// ... or the digit-planar words of a planar-resident handle (k_planar_gather, planar_resident.hpp; np_local = num_per: L counts reference
+// columns, `sh` names the shard's resident column order)
+void launch_planar_gather(u64* dst, const unsigned char* planar, size_t L0, size_t nL, int num_per, int nj, int planes, PlanarShardShape sh,
+                          hipStream_t s);
+// Step 2, decode: one workgroup per (entry of `list`, plane): the polynomials src[rec.src][plane][z] -> inverse NTT mod q0 and q1 ->
+// recenter_mod undone -> the chunk's bytes at out + rec.pos * db_item_size + plane * bytes_per_chunk (bytes past db_item_size are not
+// written; `out` is zeroed by the caller).  *undecodable += 1 per polynomial with a coefficient outside the loader's image among those
+// that carry the chunk's bytes.
+struct ItemDecodeRec {
+  int src, pos;
+};
+struct ItemDecodeDesc {
+  const u64* src;
+  const ItemDecodeRec* list;
+  uint8_t* out;
+  unsigned long long* undecodable;
+  int planes, db_item_size, bytes_per_chunk, logp;
+  u32 pt_modulus;
+};
+void launch_items_decode(const DevTables& T, const ItemDecodeDesc& d, size_t n_items, hipStream_t s);
+
 // ---- sparse buckets (lib/server SparseDb caller; sparse.hip) ----------------------------------------------------------
 // one item's bytes (device) -> `planes` packed NTT polynomials at slot_polys[plane][z]
 void launch_sparse_item_encode(const DevTables& T, const uint8_t* bytes, int item_bytes, int bytes_per_chunk, int logp,

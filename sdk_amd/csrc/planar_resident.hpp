@@ -182,4 +182,48 @@ __global__ __launch_bounds__(64) void k_planar_read(u64* out, const unsigned cha
   out[t] = w;
 }
 
+// sp_db_read_items, step 1 (item_readback.hpp): the words of the local items L0 .. L0 + nL - 1 (L = local row * num_per + REFERENCE column)
+// -> dst[L - L0][plane][z].  A workgroup owns one 16-row group of one tile's 16 resident columns -- (chunk, g, e, block, kb): 256 items --
+// for 16 z-rows of one plane: thread (z, n) reads its lane's 16 bytes of the 8 operands (modulus c, digit a), 256 contiguous bytes per
+// operand and 16 lanes, and has the 16 rows' words of column n; the items get their 128-byte z-runs from an LDS tile.
+// grid (n_rowgroups * num_per / 16, N / 16, planes); rg_lo = the first 16-row group the run touches
+constexpr int PLANAR_GATHER_Z = 16;
+__global__ __launch_bounds__(256) void k_planar_gather(u64* dst, const unsigned char* planar, size_t L0, size_t nL, int rg_lo, int num_per,
+                                                       int nj, int planes, PlanarCols pc) {
+  __shared__ u64 tile[256][PLANAR_GATHER_Z + 1];
+  const int chunks = num_per >> 7, blocks = nj >> 6;
+  const int cge = (int)(blockIdx.x % (unsigned)(chunks * 8)), rg = rg_lo + (int)(blockIdx.x / (unsigned)(chunks * 8));
+  const int e = cge & 1, g = (cge >> 1) & 3, chunk = cge >> 3;
+  const int block = rg >> 2, kb = rg & 3;
+  const int plane = blockIdx.z, z0 = blockIdx.y * PLANAR_GATHER_Z;
+  {
+    const int n = threadIdx.x & 15, zl = threadIdx.x >> 4;
+    const size_t zp = (size_t)plane * N + (size_t)(z0 + zl);
+    const mf_u32x4_t* in = reinterpret_cast<const mf_u32x4_t*>(planar);
+    u32 limb[2][16];
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+#pragma unroll
+      for (int t = 0; t < 16; t++) limb[c][t] = 0;
+#pragma unroll
+      for (int a = 0; a < 4; a++) {
+        const mf_u32x4_t o = in[planar_operand_offset(zp, chunk, g, block, e, c, a, chunks, blocks) / 16 + (size_t)(16 * kb + n)];
+#pragma unroll
+        for (int t = 0; t < 16; t++) limb[c][t] |= ((o[t >> 2] >> (8 * (t & 3))) & 0xffu) << (8 * a);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 16; t++) tile[16 * t + n][zl] = (u64)offset_digits(limb[0][t]) | ((u64)offset_digits(limb[1][t]) << 32);
+  }
+  __syncthreads();
+  const int zl = threadIdx.x & (PLANAR_GATHER_Z - 1);
+#pragma unroll 1
+  for (int pass = 0; pass < 16; pass++) {
+    const int u = pass * 16 + (threadIdx.x >> 4);   // row t = u >> 4 of the group, column n = u & 15 of the tile
+    const int ii = planar_col_ref(128 * chunk + 2 * (16 * g + (u & 15)) + e, pc);
+    const size_t L = (size_t)(16 * rg + (u >> 4)) * (size_t)num_per + (size_t)ii;
+    if (L >= L0 && L - L0 < nL) dst[((L - L0) * planes + plane) * N + z0 + zl] = tile[u][zl];
+  }
+}
+
 }  // namespace spiral

@@ -260,4 +260,21 @@ struct sp_db {
   // the handle's life: never freed and allocated again between kernels (profiles/r06_stale_staging.md)
   spiral::DevBuf<uint8_t> upload;
   std::shared_ptr<const SparseIndex> ensure_sparse_index();  // capi.cpp
+  // the handle's one READ buffer (sp_db_read_items, sp_db_export_rows; capi_readback.hpp): [counter | window list | window bytes |
+  // gathered words], at most db_load_window bytes (one item's share where that is smaller), grown before the first kernel of a call and
+  // kept for the handle's life like `upload`; sp_db_device_bytes does not count it.  The readers are read-only on everything else of
+  // the handle, so the buffer has a mutex of its own -- a reader never holds `mu` across device work and never stalls a running list --
+  // and a stream of its own, created with the buffer.
+  struct ReadBack {
+    std::mutex mu;
+    spiral::DevBuf<uint8_t> buf;
+    hipStream_t stream = nullptr;
+    ~ReadBack() {
+      if (stream) {
+        (void)hipStreamSynchronize(stream);
+        (void)hipStreamDestroy(stream);
+      }
+    }
+  };
+  mutable ReadBack readback;
 };

@@ -299,6 +299,14 @@ void launch_planar_read(u64* out, const unsigned char* planar, int plane, int z,
                      num_per, nj, planar_cols(sh, num_per));
   launched(0, "k_planar_read");
 }
+void launch_planar_gather(u64* dst, const unsigned char* planar, size_t L0, size_t nL, int num_per, int nj, int planes, PlanarShardShape sh,
+                          hipStream_t s) {
+  if (nL == 0) return;
+  const int rg_lo = (int)(L0 / (size_t)num_per) >> 4, rg_hi = (int)((L0 + nL - 1) / (size_t)num_per) >> 4;
+  hipLaunchKernelGGL(k_planar_gather, dim3((unsigned)(rg_hi - rg_lo + 1) * (unsigned)(num_per >> 4), N / PLANAR_GATHER_Z, planes), dim3(256), 0,
+                     s, dst, planar, L0, nL, rg_lo, num_per, nj, planes, planar_cols(sh, num_per));
+  launched(0, "k_planar_gather");
+}
 // The group's query tables for a pass over a planar-resident database (d.planar = its words): one tile's planar tables and offset
 // terms for 1 .. 8 queries, both tiles' for 9 .. 16.  No switch is asked: the handle's format was decided when it was created.
 void sweep_planar_resident_prepare(const DevTables& T, SweepBatchDesc& d, hipStream_t s) {

@@ -515,6 +515,35 @@ class Database:
                                   _p(out)))
         return out
 
+    def read_items(self, item0, count):
+        """items item0 .. item0 + count - 1 back out of the resident words (sp_db_read_items, the inverse of load_items and the
+        upserts) -> (bytes of count * db_item_size, present: uint8 ndarray of count, undecodable chunk polynomials).  An item this
+        handle does not hold reads as present 0 and zero bytes."""
+        size = int(self.params.get("db_item_size"))
+        out = np.zeros(max(count * size, 1), dtype=np.uint8)
+        present = np.zeros(max(count, 1), dtype=np.uint8)
+        undecodable = C.c_size_t(0)
+        _chk(lib().sp_db_read_items(_vp(self.h), C.c_size_t(item0), C.c_size_t(count), _p(out, u8p), C.c_size_t(count * size),
+                                    _p(present, u8p), C.byref(undecodable)))
+        return out[:count * size].tobytes(), present[:count], int(undecodable.value)
+
+    def export_rows(self, item0=0, count=None):
+        """the held items of the range as one /update-row body (sp_db_export_rows): dst.update_rows(src.export_rows()) moves a live
+        bucket to another format or shard count.  Raises SpiralError (rc -4) when the range holds undecodable words."""
+        if count is None:
+            count = int(self.params.get("num_items")) - item0
+        lib().sp_db_export_rows_bound.restype = C.c_size_t
+        cap = int(lib().sp_db_export_rows_bound(_vp(self.h), C.c_size_t(count)))
+        body = np.zeros(max(cap, 1), dtype=np.uint8)
+        body_len, records = C.c_size_t(0), C.c_size_t(0)
+        rc = lib().sp_db_export_rows(_vp(self.h), C.c_size_t(item0), C.c_size_t(count), _p(body, u8p), C.c_size_t(cap),
+                                     C.byref(body_len), C.byref(records))
+        if rc != 0:
+            e = SpiralError(f"libspiral_hip rc={rc}: {_err()}")
+            e.rc, e.body_len = rc, int(body_len.value)
+            raise e
+        return body[:body_len.value].tobytes()
+
     def device_bytes(self):
         return int(lib().sp_db_device_bytes(_vp(self.h)))
 
