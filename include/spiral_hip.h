@@ -244,6 +244,37 @@ size_t sp_db_export_rows_bound(const sp_db_t*, size_t count);
  * their responses decode alike, the response bytes may differ.  Threading: as sp_db_read_items. */
 int sp_db_export_rows(const sp_db_t*, size_t item0, size_t count, uint8_t* body, size_t body_cap,
                       size_t* body_len, size_t* records);
+/* A digest of the resident words, computed on the device in about one database pass: one pair of 64-bit sums per plane
+ * (plane = instance * n^2 + trial), defined over REFERENCE coordinates, so every resident format, every shard split and a sparse bucket
+ * give the same value for the same contents.  With N = 2048, w(plane, z, ii, j) the canonical word lo | hi << 32 that sp_db_read_ref
+ * returns (a word the handle does not hold -- another shard's row or column, an absent item of a sparse bucket -- counts as 0) and all
+ * arithmetic mod 2^64:
+ *     mix(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;  x = (x ^ x >> 27) * 0x94D049BB133111EB;  x ^ x >> 31
+ *     for lane l in {0, 1}:  s_l = mix(seed + l)
+ *         A_l(c) = mix(s_l ^ c) | 1,   c = (plane * N + z) * num_per + ii        (one key per (plane, z, column))
+ *         R_l(j) = mix(~s_l ^ j) | 1,  j = GLOBAL first-dimension row             (one key per row)
+ *         D_l[plane] = sum over z, ii of  A_l(c) * (sum over j of R_l(j) * w(plane, z, ii, j))
+ * out[2k], out[2k + 1] = (D_0, D_1) of plane plane0 + k.  The digest is linear in the words: the empty bucket digests to (0, 0), the
+ * digests of the shards of a bucket (row, column, planar row, sparse), added lane by lane with wrap-around, are the unsharded digest,
+ * and a sparse bucket digests like the dense one that holds the same items.  The keys are odd: changing one word changes both lanes.
+ * which: SP_DIGEST_RESIDENT = the handle's resident words; SP_DIGEST_BATCH_COPY = the digit-planar copy beside a PACKED database
+ * (sp_db_prepare_batch) while it stands: SP_E_STATE, `out` untouched, when no valid copy stands (also on a planar-resident or sparse
+ * handle).  The call never builds a copy, and pins the one it reads as a pass does, so a concurrent drop cannot free it under the kernel.
+ * plane0 < 0, plane0 + nplanes > planes, a null pointer or an unknown `which`: SP_E_ARG, nothing enqueued, nothing written.
+ * nplanes == 0: SP_OK.  Works on every handle: packed, 8-byte, planar-resident, sparse and every shard kind (a row shard sums its rows
+ * with the global j, a column shard its columns with the reference ii, a planar row shard undoes its column order, a sparse handle sums
+ * its store under one snapshot of its key map).
+ * One kernel per resident form, each reading every resident byte of the plane range once.  Read-only, threading as sp_db_read_items:
+ * beside queries and other readers of the handle, not beside a writer.  It takes its turn at the handle's read buffer and stream (the
+ * partial sums and the row keys live there); nothing is allocated or freed between the kernels of a call. */
+#define SP_DIGEST_RESIDENT 0
+#define SP_DIGEST_BATCH_COPY 1
+int sp_db_digest(const sp_db_t*, uint64_t seed, int which, int plane0, int nplanes, uint64_t* out /* 2 * nplanes */);
+/* The same sums on the HOST, from words in the reference layout: adds to acc[0], acc[1] the contribution of rows z0 .. z0 + nz - 1 of
+ * one plane, words[z - z0][ii][j] with the full dim0 -- exactly what sp_db_load_plane takes -- after reducing both 32-bit limbs mod
+ * their primes as the loaders do.  No device call: works with no GPU present.  A host that streams a database through
+ * sp_db_load_plane accumulates this beside the upload and compares with sp_db_digest afterwards. */
+int sp_db_digest_ref_words(const sp_params_t*, uint64_t seed, int plane, int z0, int nz, const uint64_t* words, uint64_t acc[2]);
 size_t sp_db_device_bytes(const sp_db_t*);      /* the resident database words */
 size_t sp_db_batch_copy_bytes(const sp_db_t*);  /* the digit-planar copy beside them while it stands (sp_db_prepare_batch), else 0 */
 

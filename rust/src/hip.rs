@@ -95,6 +95,8 @@ pub mod sys {
         pub fn sp_db_read_items(db: *const sp_db_t, item0: usize, count: usize, out: *mut u8, out_cap: usize, present: *mut u8, undecodable: *mut usize) -> c_int;
         pub fn sp_db_export_rows_bound(db: *const sp_db_t, count: usize) -> usize;
         pub fn sp_db_export_rows(db: *const sp_db_t, item0: usize, count: usize, body: *mut u8, body_cap: usize, body_len: *mut usize, records: *mut usize) -> c_int;
+        pub fn sp_db_digest(db: *const sp_db_t, seed: u64, which: c_int, plane0: c_int, nplanes: c_int, out: *mut u64) -> c_int;
+        pub fn sp_db_digest_ref_words(p: *const sp_params_t, seed: u64, plane: c_int, z0: c_int, nz: c_int, words: *const u64, acc: *mut u64) -> c_int;
         pub fn sp_db_device_bytes(db: *const sp_db_t) -> usize;
         // ---- PublicParameters (client.rs:146-259)
         pub fn sp_pp_deserialize(p: *const sp_params_t, data: *const u8, len: usize) -> *mut sp_pp_t;
@@ -417,6 +419,16 @@ impl Database {
         check(unsafe { sys::sp_db_export_rows(self.0, item0, count, body.as_mut_ptr(), body.len(), &mut len, &mut records) })?;
         body.truncate(len);
         Ok(body)
+    }
+    /// One pair of 64-bit sums per plane over the resident words (`sp_db_digest`), planes `plane0 .. plane0 + nplanes`: the same value on
+    /// every format, shard split and sparse bucket for the same contents; the shards' digests add up (wrapping) to the unsharded one.
+    /// `batch_copy`: digest the digit-planar copy beside a PACKED database instead (`SP_E_STATE` when none stands).
+    pub fn digest(&self, seed: u64, batch_copy: bool, plane0: usize, nplanes: usize) -> Result<Vec<[u64; 2]>, HipError> {
+        let mut out = vec![[0u64; 2]; nplanes];
+        check(unsafe {
+            sys::sp_db_digest(self.0, seed, batch_copy as c_int, plane0 as c_int, nplanes as c_int, out.as_mut_ptr() as *mut u64)
+        })?;
+        Ok(out)
     }
     pub fn device_bytes(&self) -> usize {
         unsafe { sys::sp_db_device_bytes(self.0) }

@@ -23,6 +23,7 @@ from .spiral import (
     SpiralError,
     build_library,
     coefficient_expansion,
+    digest_ref_words,
     encode,
     expand_query,
     fold_ciphertexts,

@@ -1612,6 +1612,7 @@ int sp_process_query(const sp_params_t* h, const sp_pp_t* pp, const uint8_t* que
 }  // extern "C"
 
 #include "capi_readback.hpp"   // sp_db_read_items, sp_db_export_rows_bound, sp_db_export_rows
+#include "capi_digest.hpp"     // sp_db_digest, sp_db_digest_ref_words
 
 // The build lists of this tree (Makefile, tests/emu/build_emulated_library.py) compile capi_batch.cpp and capi_stage.cpp as
 // translation units of their own and say so with SPIRAL_CAPI_SPLIT.  A list that names capi.cpp alone, as every list did before the

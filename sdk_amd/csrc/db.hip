@@ -388,3 +388,4 @@ void launch_sweep_out_to_ref(u64* out, const u32* in, int num_per, hipStream_t s
 }  // namespace spiral
 
 #include "item_readback.hpp"   // sp_db_read_items: gather + decode, the item loaders above read backwards
+#include "db_digest.hpp"      // sp_db_digest: the kernels over 8-byte words, PACKED units and a sparse store

@@ -635,4 +635,40 @@ __host__ __device__ inline u64 synth_word(u64 seed, u64 idx) {
   return lo | (hi << 32);
 }
 
+// ---- database digest (sp_db_digest; db_digest.hpp, db_digest_planar.hpp, capi_digest.hpp) -----------------------------------------
+// One pair of 64-bit sums per plane over REFERENCE coordinates, all arithmetic mod 2^64, lane l in {0, 1}:
+//     s_l = mix(seed + l),  A_l(c) = mix(s_l ^ c) | 1,  c = (plane * N + z) * num_per + ii,  R_l(j) = mix(~s_l ^ j) | 1, j = global row
+//     D_l[plane] = sum over z, ii of A_l(c) * (sum over j of R_l(j) * w(plane, z, ii, j)),   w = canonical lo | hi << 32
+// linear in the words, additive over shards, the same on every resident form.  mix is synth_word's finalizer.
+__host__ __device__ inline u64 digest_mix(u64 x) {
+  x += 0x9E3779B97F4A7C15ULL;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+  return x ^ (x >> 31);
+}
+__host__ __device__ inline u64 digest_col_key(u64 s, u64 c) { return digest_mix(s ^ c) | 1ULL; }
+__host__ __device__ inline u64 digest_row_key(u64 s, u64 j) { return digest_mix(~s ^ j) | 1ULL; }
+constexpr int DIGEST_ROWS = 1024;   // rows of R a workgroup keeps in LDS (2 lanes x 8 bytes each); taller handles are cut into row tiles
+// what every digest kernel is given: sums[2 * (plane - plane0) + l] receives the workgroups' partial sums (wrapping atomic adds; zeroed by
+// launch_digest_keys), R[l * nj + jl] = R_l(j0 + jl) for the handle's local rows, s[l] the lane seeds
+struct DigestDesc {
+  unsigned long long* sums;
+  const u64* R;
+  u64 s[2];
+  int plane0, nplanes;
+  int num_per;   // columns of the REFERENCE (the c of a column key)
+  int nj;        // local rows
+};
+// sums[0 .. 2 nplanes) = 0 and R[l * nj + jl] = R_l(j0 + jl): the first kernel of a call
+void launch_digest_keys(unsigned long long* sums, u64* R, u64 seed, int nplanes, int j0, int nj, hipStream_t s);
+// 8-byte words [plane][z][jl][il] (np_local columns, local column il = reference column cm.off + cm.stride * il) / the PACKED unit stream
+void launch_digest_words(const DigestDesc& d, const u64* db, int np_local, int packed, ColMap cm, hipStream_t s);
+// a sparse store [slot][planes][z]: list[k] = {slot, item index j * num_per + ii} for the n stored items (device memory)
+struct DigestSlotRec {
+  unsigned long long slot, item;
+};
+void launch_digest_sparse(const DigestDesc& d, const u64* polys, int planes, const DigestSlotRec* list, size_t n, hipStream_t s);
+// digit-planar words (a planar-resident handle, a planar row shard `sh`, the batch copy of a PACKED database: sh = {}); sweep_planar.hip
+void launch_digest_planar(const DigestDesc& d, const unsigned char* planar, PlanarShardShape sh, hipStream_t s);
+
 }  // namespace spiral

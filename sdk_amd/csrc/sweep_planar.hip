@@ -10,6 +10,7 @@
 #include "sweep_mfma_scatter.hpp"
 #include "sweep_narrow_batch.hpp"
 #include "planar_resident.hpp"
+#include "db_digest_planar.hpp"
 #include "server.hpp"
 
 namespace spiral {
@@ -306,6 +307,16 @@ void launch_planar_gather(u64* dst, const unsigned char* planar, size_t L0, size
   hipLaunchKernelGGL(k_planar_gather, dim3((unsigned)(rg_hi - rg_lo + 1) * (unsigned)(num_per >> 4), N / PLANAR_GATHER_Z, planes), dim3(256), 0,
                      s, dst, planar, L0, nL, rg_lo, num_per, nj, planes, planar_cols(sh, num_per));
   launched(0, "k_planar_gather");
+}
+// sp_db_digest over digit-planar words: about 32 sixteen-row groups per thread where the plane has that many, so a workgroup's copy of the
+// row keys is read many times over
+void launch_digest_planar(const DigestDesc& d, const unsigned char* planar, PlanarShardShape sh, hipStream_t s) {
+  if (d.nplanes <= 0 || d.nj <= 0) return;
+  if (d.nj > DIGEST_ROWS) throw HipError("internal: a planar database of more than DIGEST_ROWS rows");
+  const size_t groups = (size_t)N * (size_t)d.num_per * (size_t)(d.nj >> 4);
+  const unsigned wgs = (unsigned)std::max<size_t>(1, std::min<size_t>((groups + 255) / 256, std::max<size_t>(4096, groups / (256 * 32))));
+  hipLaunchKernelGGL(k_digest_planar, dim3(wgs, d.nplanes), dim3(256), 0, s, d, planar, planar_cols(sh, d.num_per));
+  launched(0, "k_digest_planar");
 }
 // The group's query tables for a pass over a planar-resident database (d.planar = its words): one tile's planar tables and offset
 // terms for 1 .. 8 queries, both tiles' for 9 .. 16.  No switch is asked: the handle's format was decided when it was created.

@@ -544,12 +544,47 @@ class Database:
             raise e
         return body[:body_len.value].tobytes()
 
+    def digest(self, seed, which="resident", plane0=0, nplanes=None, out=None):
+        """one pair of 64-bit sums per plane over the resident words, computed on the device in about one database pass
+        (sp_db_digest) -> uint64 ndarray [nplanes][2].  Defined over reference coordinates: every format, every shard split and a
+        sparse bucket give the same value for the same contents, and the shards' digests add up (wrapping) to the unsharded one.
+        which: "resident", or "batch_copy" = the digit-planar copy beside a PACKED database while it stands (SpiralError with
+        rc -4 when none does).  `out` (optional): a C-contiguous uint64 array of 2 * nplanes that receives the result; an error
+        leaves it untouched.  The exception carries the library's `rc`."""
+        code = {"resident": 0, "batch_copy": 1}.get(which, which)
+        if nplanes is None:
+            nplanes = self.params.instances * self.params.n * self.params.n - plane0
+        if out is None:
+            out = np.zeros((max(nplanes, 0), 2), dtype=np.uint64)
+        rc = lib().sp_db_digest(_vp(self.h), C.c_uint64(seed), C.c_int(code), C.c_int(plane0), C.c_int(nplanes), _p(out))
+        if rc != 0:
+            e = SpiralError(f"libspiral_hip rc={rc}: {_err()}")
+            e.rc = rc
+            raise e
+        return out.reshape(-1, 2)[:max(nplanes, 0)]
+
     def device_bytes(self):
         return int(lib().sp_db_device_bytes(_vp(self.h)))
 
     def batch_copy_bytes(self):
         """bytes of the digit-planar copy beside the resident words while it stands (prepare_batch), else 0"""
         return int(lib().sp_db_batch_copy_bytes(_vp(self.h)))
+
+
+def digest_ref_words(params, seed, plane, z0, words, acc=None):
+    """the digest of Database.digest on the HOST, from reference-layout words (sp_db_digest_ref_words; no device call): adds to `acc`
+    (uint64 ndarray of 2, default zeros) the contribution of rows z0 .. z0 + nz - 1 of one plane, words[nz][num_per][dim0] -- what
+    load_plane takes -- with both limbs reduced as the loaders reduce them.  Returns acc."""
+    w = _u64arr(words)
+    per_z = params.num_per * params.dim0
+    if per_z == 0 or w.size % per_z:
+        raise SpiralError("digest_ref_words: words are not whole z-rows of num_per * dim0 words")
+    acc = np.zeros(2, dtype=np.uint64) if acc is None else acc
+    if acc.dtype != np.uint64 or acc.size != 2 or not acc.flags.c_contiguous:
+        raise SpiralError("digest_ref_words: acc is a C-contiguous uint64 array of 2")
+    _chk(lib().sp_db_digest_ref_words(_vp(params.h), C.c_uint64(seed), C.c_int(plane), C.c_int(z0), C.c_int(w.size // per_z), _p(w),
+                                      _p(acc)))
+    return acc
 
 
 def synth_word(seed, ref_index):
