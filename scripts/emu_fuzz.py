@@ -1,8 +1,9 @@
 """Differential fuzzing of the library's sources on the emulated device against the oracle (CPU only, test infrastructure).
 
-Random VALID parameter sets (gadget widths, moduli sizes, instances, pack version, item sizes, nu_1 <= 7, nu_2 <= 8), random
-item index and key / query seeds; response bytes of sp_process_query (and, on PACKED shapes, of a list through
-sp_process_query_batch) must equal the oracle's.  Usage:
+Random VALID parameter sets (n = 2, 3 and 4, gadget widths, moduli sizes, plaintext moduli from 4 to 512 and 65536, instances, pack
+version, item sizes, nu_1 <= 7, nu_2 <= 8, at most 12 * 2^13 plane-items), random item index and key / query seeds; response bytes
+of sp_process_query (and, on PACKED shapes, of a list through sp_process_query_batch, once more on a planar-resident handle where
+that format exists) must equal the oracle's.  Usage:
     SPIRAL_HIP_LIB=tests/emu/_build/libspiral_emu.so python scripts/emu_fuzz.py [--seed S] [--minutes M]
     python scripts/emu_fuzz.py --device [--seed S] [--minutes M]      (the same cases against the real library on a GPU box)
 Prints one line per case; a mismatch prints the configuration as JSON (paste it into tests/test_gpu_parity.py::_FUZZ) and exits 1.
@@ -27,7 +28,8 @@ def valid(c):
 
 def draw(rng):
     while True:
-        c = dict(n=2, nu_1=int(rng.integers(2, 8)), nu_2=int(rng.integers(0, 9)), p=int(rng.choice([4, 16, 64, 256, 256, 256])),
+        c = dict(n=int(rng.choice([2, 2, 2, 3, 4])), nu_1=int(rng.integers(2, 8)), nu_2=int(rng.integers(0, 9)),
+                 p=int(rng.choice([4, 16, 64, 256, 256, 256, 512, 65536])),
                  q2_bits=int(rng.integers(14, 29)), t_gsw=int(rng.choice([1, 2, 3, 4, 5, 7, 8, 9, 10, 14, 28])),
                  t_conv=int(rng.choice([1, 2, 3, 4, 5, 7, 14, 28])), t_exp_left=int(rng.choice([2, 3, 4, 5, 6, 7, 8, 14, 16, 28])),
                  t_exp_right=int(rng.choice([2, 4, 5, 8, 9, 14, 19, 28, 56])), instances=int(rng.choice([1, 1, 1, 2, 3])),
@@ -37,6 +39,9 @@ def draw(rng):
         if rng.random() < 0.1:
             c["direct_upload"] = 1
         if c["nu_1"] + c["nu_2"] > 13:
+            continue
+        # n = 3 and 4 multiply the planes: keep the oracle's words (16 KiB per plane and item) at what n = 2 reached, 1.6 GB
+        if c["instances"] * c["n"] ** 2 << (c["nu_1"] + c["nu_2"]) > 12 << 13:
             continue
         if valid(c):
             return c
@@ -108,6 +113,21 @@ def main():
             paths = sorted(set(paths) | sp.paths_taken())
             ok = outs == wants
             extra = wire + " list%d" % B
+            if ok and cfg["nu_1"] >= 6 and cfg["nu_2"] >= 7:
+                # the same list on a planar-resident handle where the format exists (dim0 % 64 == 0, num_per % 128 == 0): the writers
+                # of planar_resident.hpp and k_sweep_planar at this plane count
+                try:
+                    gpl = sp.Database.planar(p)
+                except sp.SpiralError as e:      # (say so: a format that is wrongly refused must show up in the log)
+                    gpl = None
+                    extra += " planar-refused(%s)" % str(e)[-60:]
+                if gpl is not None:
+                    gpl.load(db)
+                    sp.paths_taken()
+                    ok = sp.process_query_batch(p, gpp, lst, gpl) == wants
+                    paths = sorted(set(paths) | sp.paths_taken())
+                    extra += " planar"
+                    del gpl
         if ok and rng.random() < 0.3 and not cfg.get("direct_upload") and cfg["p"] == 256:   # (lib/server stores bytes: p = 256)
             # lib/server's sparse bucket (SparseDb + update_item_raw; pruned expansion, present-items-only multiply, fold
             # shortcuts) against oracle/sparse_server.cpp, a random fraction of the items present

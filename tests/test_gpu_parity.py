@@ -1447,6 +1447,10 @@ _FUZZ = [
     dict(n=2, nu_1=5, nu_2=4, p=256, q2_bits=20, t_gsw=4, t_conv=2, t_exp_left=2, t_exp_right=2, instances=1, db_item_size=8192),
     dict(n=2, nu_1=4, nu_2=5, p=256, q2_bits=20, t_gsw=2, t_conv=1, t_exp_left=3, t_exp_right=4, instances=1, db_item_size=2048),
     dict(n=2, nu_1=6, nu_2=4, p=256, q2_bits=20, t_gsw=28, t_conv=28, t_exp_left=28, t_exp_right=56, instances=1, db_item_size=8192),
+    # n != 2 and p = 512 through expansion, fold and pack (the sets of tests/param_matrix.py: N3, V0's gadgets, S16), single queries
+    dict(n=3, nu_1=6, nu_2=4, p=256, q2_bits=20, t_gsw=4, t_conv=4, t_exp_left=8, t_exp_right=56, instances=1, db_item_size=18432),
+    dict(n=4, nu_1=5, nu_2=3, p=256, q2_bits=20, t_gsw=8, t_conv=4, t_exp_left=8, t_exp_right=56, instances=1, db_item_size=32768),
+    dict(n=2, nu_1=6, nu_2=2, p=512, q2_bits=21, t_gsw=10, t_conv=4, t_exp_left=16, t_exp_right=56, instances=3, db_item_size=27000),
 ]
 
 
