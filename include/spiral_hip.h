@@ -45,6 +45,7 @@ extern "C" {
 
 typedef struct sp_params sp_params_t; /* spiral_rs::params::Params           params.rs:49-82   */
 typedef struct sp_pp sp_pp_t;         /* spiral_rs::client::PublicParameters client.rs:146-152 */
+typedef struct sp_ppc sp_ppc_t;       /* a client's public parameters as sent: the wire image on the device, not expanded */
 typedef struct sp_db sp_db_t;         /* the `db: &[u64]` argument of process_query, device-resident */
 typedef struct sp_query sp_query_t;   /* one in-flight query (expanded), for the multi-GPU split */
 
@@ -287,6 +288,26 @@ void sp_pp_free(sp_pp_t*);
 /* NTT-form matrices in wire order, ref layout (tests): v_packing[n], v_expansion_left[g],
  * v_expansion_right[stop_round+1] (if present on the wire), v_conversion[1]. */
 int sp_pp_export(const sp_pp_t*, uint64_t* out, size_t cap_words, size_t* n_words);
+/* What an expanded handle keeps on the device: the NTT-form matrices, their wave-layout twin (where the params expand queries) and
+ * the concatenated packing matrices.  The same for a handle of sp_pp_deserialize and of sp_pp_expand. */
+size_t sp_pp_device_bytes(const sp_pp_t*);
+
+/* The COMPACT form of a client's public parameters: the wire image itself, uploaded and kept on the device (row 0 of every matrix is
+ * the 32-byte seed, the other rows are the client's words), about a quarter of what the expanded handle holds.  len must equal
+ * setup_bytes: checked before any device work.  sp_pp_compact uploads and does nothing else; nothing is validated beyond the length,
+ * as in sp_pp_deserialize (words >= Q stay as sent). */
+sp_ppc_t* sp_pp_compact(const sp_params_t*, const uint8_t* data, size_t len);
+void sp_ppc_free(sp_ppc_t*);
+size_t sp_ppc_device_bytes(const sp_ppc_t*); /* the image: setup_bytes, rounded up to the allocation's granule */
+/* The device-side inverse of the wire format (k_pp_raw_image: ChaCha20 keystream, Q - (ks % Q), the wire's rows; then the forward
+ * transform and the two derived layouts, the launches of sp_pp_deserialize): a fresh handle, word for word the one
+ * sp_pp_deserialize builds from the same bytes, taken by every entry point that takes that one. */
+sp_pp_t* sp_pp_expand(const sp_ppc_t*);
+/* The same INTO an expanded handle of the same params and device (from sp_pp_deserialize or sp_pp_expand), overwriting the client it
+ * held: nothing is allocated or freed on the device (the raw image is staged in a buffer the library keeps per params and device),
+ * and the call waits for its own work only.  The caller sees to it that no query that reads `slot` is in flight.  A slot of other
+ * params or of another device, or a null argument: SP_E_ARG, the slot is as it was. */
+int sp_pp_expand_into(const sp_ppc_t*, sp_pp_t* slot);
 
 /* ---------------------------------------------------------- process_query
  * server.rs:650-741 process_query(params, public_params, query, db) -> Vec<u8>, with
@@ -505,6 +526,19 @@ size_t sp_server_private_read_json_bound(const sp_server_t*, int n_queries); /* 
  * reply {"status":"done updating", "loading_time_us":N, "largest_update":M} (NUL-terminated; 128 bytes always suffice).  A faulty
  * record: sp_db_update_rows' status and text, the prefix applied, nothing written to out. */
 int sp_server_update_row(sp_server_t*, sp_db_t* db, const uint8_t* body, size_t body_len, char* out, size_t out_cap, size_t* out_len);
+/* Compact client registry.  max_expanded = 0 (the default): every client is expanded at /setup and stays so until it is forgotten.
+ * max_expanded = k > 0 (only while the server has no clients, else SP_E_ARG): /setup keeps the COMPACT handle (sp_pp_compact) only, and
+ * the server owns at most k expanded slots, allocated on first use and kept until sp_server_free.  /private-read, per distinct uuid
+ * of its list: an expanded client is a HIT (its slot is pinned for the request and becomes the most recently used); otherwise a MISS
+ * takes an unallocated slot, else the least recently used unpinned one (an EVICTION), and expands into it (sp_pp_expand_into); when
+ * every slot is pinned by this or a concurrent request the client is expanded into a temporary handle that lives for the request (an
+ * OVERFLOW): a request never fails because of k.  sp_server_forget drops the compact image; the client's slot is free once unpinned.
+ * Direct-upload params with k > 0: the public parameters of a request element are copied into the slot's own wire buffer
+ * (setup_bytes, kept) and expanded into the slot; elements beyond the free slots overflow; sp_server_clients stays 0. */
+int sp_server_set_expanded_clients(sp_server_t*, size_t max_expanded);
+/* out: registered clients, clients expanded now, hits, misses, evictions, overflows, device bytes of all compact images plus all
+ * allocated slots.  With max_expanded = 0 registered == expanded and the bytes are those of the expanded handles. */
+int sp_server_client_stats(const sp_server_t*, uint64_t out[7]);
 
 /* Stand-alone timed sweep for the roofline measurement: issues the db-sweep launches of one query over `db`
  * (the same kernel and launch shapes sp_process_query uses) `iters` times with the query slice of `q`, HIP events
@@ -544,6 +578,9 @@ int sp_debug_resident_check(const sp_params_t* params, const sp_pp_t* pp, uint64
  * what regenerates row 0 of the public parameters and of a query; no GPU needed): tests compare it with the RFC 8439-pinned
  * restatement word for word, on lengths that exercise the eight-block AVX2 body and the one-block tail. */
 int sp_debug_chacha20_u64(const uint8_t seed[32], uint64_t* out, size_t count);
+/* The same stream from the DEVICE's generator (k_pp_raw_image, what sp_pp_expand regenerates row 0 with): words first_word ..
+ * first_word + count - 1; first_word % 8 == 0 (a ChaCha block is 8 words), any count, 0 included.  Needs a GPU. */
+int sp_debug_chacha20_u64_device(const sp_params_t*, const uint8_t seed[32], size_t first_word, uint64_t* out, size_t count);
 
 /* Profiling aid: nanoseconds per 2048-point forward NTT of the transform core alone (M = 1, 2 or 4 coefficient
  * vectors per thread, `blocks` workgroups each chaining `reps` transforms, no memory traffic but twiddles). */

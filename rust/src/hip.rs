@@ -32,6 +32,10 @@ pub mod sys {
         _p: [u8; 0],
     }
     #[repr(C)]
+    pub struct sp_ppc_t {
+        _p: [u8; 0],
+    }
+    #[repr(C)]
     pub struct sp_db_t {
         _p: [u8; 0],
     }
@@ -102,6 +106,13 @@ pub mod sys {
         pub fn sp_pp_deserialize(p: *const sp_params_t, data: *const u8, len: usize) -> *mut sp_pp_t;
         pub fn sp_pp_free(pp: *mut sp_pp_t);
         pub fn sp_pp_export(pp: *const sp_pp_t, out: *mut u64, cap_words: usize, n_words: *mut usize) -> c_int;
+        pub fn sp_pp_device_bytes(pp: *const sp_pp_t) -> usize;
+        // ---- compact clients: the wire image kept on the device, expanded there on demand
+        pub fn sp_pp_compact(p: *const sp_params_t, data: *const u8, len: usize) -> *mut sp_ppc_t;
+        pub fn sp_ppc_free(c: *mut sp_ppc_t);
+        pub fn sp_ppc_device_bytes(c: *const sp_ppc_t) -> usize;
+        pub fn sp_pp_expand(c: *const sp_ppc_t) -> *mut sp_pp_t;
+        pub fn sp_pp_expand_into(c: *const sp_ppc_t, slot: *mut sp_pp_t) -> c_int;
         // ---- process_query (server.rs:650-741)
         pub fn sp_process_query(p: *const sp_params_t, pp: *const sp_pp_t, query: *const u8, query_len: usize, db: *const sp_db_t,
                                 out: *mut u8, out_cap: usize, out_len: *mut usize) -> c_int;
@@ -163,6 +174,8 @@ pub mod sys {
         pub fn sp_server_setup_json(s: *mut sp_server_t, body: *const c_char, body_len: usize, out: *mut c_char, out_cap: usize,
                                     out_len: *mut usize) -> c_int;
         pub fn sp_server_forget(s: *mut sp_server_t, uuid: *const c_char) -> c_int;
+        pub fn sp_server_set_expanded_clients(s: *mut sp_server_t, max_expanded: usize) -> c_int;
+        pub fn sp_server_client_stats(s: *const sp_server_t, out7: *mut u64) -> c_int;
         pub fn sp_server_private_read(s: *mut sp_server_t, requests: *const *const u8, request_lens: *const usize, n: c_int,
                                       out: *mut u8, out_stride: usize, out_lens: *mut usize) -> c_int;
         pub fn sp_server_private_read_json(s: *mut sp_server_t, body: *const c_char, body_len: usize, out: *mut c_char,
@@ -182,6 +195,8 @@ pub mod sys {
         pub fn sp_debug_cu_probe(bit_lo: c_int, bit_hi: c_int, blocks: c_int, out2: *mut u32) -> c_int;
         pub fn sp_debug_resident_check(params: *const sp_params_t, pp: *const sp_pp_t, out: *mut u64, cap: c_int) -> c_int;
         pub fn sp_debug_chacha20_u64(seed: *const u8, out: *mut u64, count: usize) -> c_int;
+        pub fn sp_debug_chacha20_u64_device(p: *const sp_params_t, seed: *const u8, first_word: usize, out: *mut u64,
+                                            count: usize) -> c_int;
         pub fn sp_bench_ntt(p: *const sp_params_t, m: c_int, blocks: c_int, reps: c_int, ns_per_ntt: *mut f32) -> c_int;
         // ---- stage level, 1:1 with the reference's pub functions (host arrays in the reference layouts)
         pub fn sp_ntt_forward(p: *const sp_params_t, data: *mut u64, count: usize) -> c_int;
@@ -248,6 +263,10 @@ const CRT: usize = 2;
 pub struct Params(*mut sys::sp_params_t);
 /// `spiral_rs::client::PublicParameters` (client.rs:146-152), NTT'd and device resident.
 pub struct PublicParameters(*mut sys::sp_pp_t);
+/// A client's public parameters as sent, resident on the device and not expanded (`sp_pp_compact`).
+pub struct CompactPublicParameters(*mut sys::sp_ppc_t);
+unsafe impl Send for CompactPublicParameters {}
+unsafe impl Sync for CompactPublicParameters {}
 /// The `db: &[u64]` argument of `process_query`, registered once and resident in HBM.
 pub struct Database(*mut sys::sp_db_t);
 /// One RCCL rank (one process per GPU).
@@ -316,6 +335,46 @@ impl PublicParameters {
 impl Drop for PublicParameters {
     fn drop(&mut self) {
         unsafe { sys::sp_pp_free(self.0) }
+    }
+}
+impl PublicParameters {
+    /// What the expanded handle keeps on the device (`sp_pp_device_bytes`).
+    pub fn device_bytes(&self) -> usize {
+        unsafe { sys::sp_pp_device_bytes(self.0) }
+    }
+}
+
+impl CompactPublicParameters {
+    /// The wire image uploaded and kept as it is (`sp_pp_compact`); `data.len()` must be `setup_bytes`.
+    pub fn try_new(params: &Params, data: &[u8]) -> Result<Self, HipError> {
+        let h = unsafe { sys::sp_pp_compact(params.0, data.as_ptr(), data.len()) };
+        if h.is_null() {
+            Err(HipError { code: sys::SP_E_ARG, message: last_error() })
+        } else {
+            Ok(CompactPublicParameters(h))
+        }
+    }
+    pub fn device_bytes(&self) -> usize {
+        unsafe { sys::sp_ppc_device_bytes(self.0) }
+    }
+    /// A fresh expanded handle, word for word what `PublicParameters::deserialize` builds from the same bytes.
+    pub fn expand(&self) -> Result<PublicParameters, HipError> {
+        let h = unsafe { sys::sp_pp_expand(self.0) };
+        if h.is_null() {
+            Err(HipError { code: sys::SP_E_ARG, message: last_error() })
+        } else {
+            Ok(PublicParameters(h))
+        }
+    }
+    /// Overwrite `slot` (same params and device) with this client: nothing is allocated or freed on the device.  `&mut`: no
+    /// query reading the slot may be in flight.
+    pub fn expand_into(&self, slot: &mut PublicParameters) -> Result<(), HipError> {
+        check(unsafe { sys::sp_pp_expand_into(self.0, slot.0) })
+    }
+}
+impl Drop for CompactPublicParameters {
+    fn drop(&mut self) {
+        unsafe { sys::sp_ppc_free(self.0) }
     }
 }
 
@@ -664,6 +723,19 @@ impl<'a> Server<'a> {
         check(sys::sp_server_update_row(self.h, self._db.0, body.as_ptr(), body.len(), out.as_mut_ptr() as *mut c_char, out.len(), &mut n))?;
         out.truncate(n);
         Ok(String::from_utf8(out).unwrap())
+    }
+}
+impl<'a> Server<'a> {
+    /// `k > 0` (only while the server has no clients): clients are kept compact and at most `k` are expanded at a time, on demand;
+    /// 0: every client is expanded at /setup (the default).
+    pub fn set_expanded_clients(&self, k: usize) -> Result<(), HipError> {
+        check(unsafe { sys::sp_server_set_expanded_clients(self.h, k) })
+    }
+    /// registered, expanded now, hits, misses, evictions, overflows, device bytes of the compact images plus the slots
+    pub fn client_stats(&self) -> Result<[u64; 7], HipError> {
+        let mut out = [0u64; 7];
+        check(unsafe { sys::sp_server_client_stats(self.h, out.as_mut_ptr()) })?;
+        Ok(out)
     }
 }
 impl<'a> Drop for Server<'a> {

@@ -11,6 +11,7 @@ from .spiral import (
     scalar_multiply,
     bench_sweep_batch,  # noqa: F401
     bench_sweep_scatter_group,  # noqa: F401
+    CompactPublicParameters,
     Database,
     Params,
     PolyMatrixNTT,

@@ -315,3 +315,5 @@ void launch_cu_probe(u32* out, int blocks, hipStream_t s) {
 }
 
 }  // namespace spiral
+
+#include "pp_raw_image.hpp"   // k_pp_raw_image: a client's raw public parameters from the wire image (sp_pp_expand)

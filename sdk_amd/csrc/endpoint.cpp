@@ -26,6 +26,7 @@
 #include "../../include/spiral_hip.h"
 
 extern "C" void sp_set_last_error_(const char* msg);  // capi.cpp
+extern "C" int sp_ppc_assign_(sp_ppc_t* c, const uint8_t* data, size_t len);  // capi_compact.hpp: overwrite a compact handle's image
 
 namespace {
 
@@ -177,6 +178,23 @@ struct sp_server {
   std::unordered_map<std::string, std::shared_ptr<sp_pp_t>> pub_params;
   // bin/server.rs:24 RwLock<SparseDb>: /private-read holds it shared for its whole list (:102), /update-row exclusively (:35)
   mutable std::shared_mutex db_mu;
+  // ---- compact registry (sp_server_set_expanded_clients(k > 0)): every client is kept as its wire image on the device, at most
+  // max_expanded of them are expanded at a time, into slots the server allocates on first use and keeps.  Everything below is under
+  // reg_mu, expansions into slots included: one expansion runs at a time on a device anyway (its staging buffer is the device's one).
+  // A request pins the slots it reads until it has been answered; only a slot nobody pins is recycled.
+  size_t max_expanded = 0;
+  struct Slot {
+    std::shared_ptr<sp_pp_t> pp;     // the expanded handle: sp_pp_expand the first time, sp_pp_expand_into from then on
+    std::shared_ptr<sp_ppc_t> wire;  // direct-upload params: the slot's own wire buffer (setup_bytes), overwritten per request element
+    std::string owner;               // the uuid whose parameters the slot holds; empty: nobody's (never used, forgotten, direct upload)
+    int pins = 0;
+    uint64_t used = 0;               // the registry's clock at the last hit or expansion; 0 once the owner is forgotten
+  };
+  mutable std::mutex reg_mu;
+  std::unordered_map<std::string, std::shared_ptr<sp_ppc_t>> compact;
+  std::unordered_map<std::string, size_t> slot_of;  // the expanded clients
+  std::vector<Slot> slots;                          // capacity max_expanded from the start: never reallocated
+  uint64_t clock = 0, hits = 0, misses = 0, evictions = 0, overflows = 0;
 };
 
 template <typename F>
@@ -204,6 +222,136 @@ static std::shared_ptr<sp_pp_t> deserialize_pp(const sp_server& S, const uint8_t
   return std::shared_ptr<sp_pp_t>(pp, [](sp_pp_t* x) { sp_pp_free(x); });
 }
 
+static std::shared_ptr<sp_ppc_t> compact_pp(const sp_server& S, const uint8_t* data, size_t len) {
+  if (len != S.setup_bytes)
+    throw Fail{SP_E_ARG, "public parameters: " + std::to_string(len) + " bytes, setup_bytes is " + std::to_string(S.setup_bytes)};
+  sp_ppc_t* c = sp_pp_compact(S.params, data, len);
+  if (!c) throw Fail{SP_E_ARG, std::string("sp_pp_compact: ") + sp_last_error()};
+  return std::shared_ptr<sp_ppc_t>(c, [](sp_ppc_t* x) { sp_ppc_free(x); });
+}
+static std::shared_ptr<sp_pp_t> expand_pp(const sp_ppc_t* c) {
+  sp_pp_t* pp = sp_pp_expand(c);
+  if (!pp) throw Fail{SP_E_ARG, std::string("sp_pp_expand: ") + sp_last_error()};
+  return std::shared_ptr<sp_pp_t>(pp, [](sp_pp_t* x) { sp_pp_free(x); });
+}
+
+// POST /setup after decoding: the client under a fresh uuid -- expanded (max_expanded = 0) or as its compact image
+static std::string register_client(sp_server& S, const uint8_t* data, size_t len) {
+  bool compact;
+  {
+    std::lock_guard<std::mutex> lk(S.reg_mu);
+    compact = S.max_expanded > 0;
+  }
+  if (compact) {
+    auto c = compact_pp(S, data, len);
+    const std::string id = uuid_v4();
+    std::lock_guard<std::mutex> lk(S.reg_mu);
+    S.compact[id] = std::move(c);
+    return id;
+  }
+  auto pp = deserialize_pp(S, data, len);
+  const std::string id = uuid_v4();
+  std::unique_lock<std::shared_mutex> lk(S.mu);
+  S.pub_params[id] = std::move(pp);
+  return id;
+}
+
+// the slots a request has pinned, released when it has been answered (or has failed)
+struct Pins {
+  sp_server& S;
+  std::vector<size_t> held;
+  explicit Pins(sp_server& s) : S(s) {}
+  ~Pins() {
+    std::lock_guard<std::mutex> lk(S.reg_mu);
+    for (size_t i : held) S.slots[i].pins--;
+  }
+};
+
+// a slot for a miss (caller holds reg_mu): an unallocated one, else the least recently used one nobody pins (a forgotten client's
+// first), its owner evicted; -1: every slot is pinned
+static long take_slot(sp_server& S) {
+  long idx = -1;
+  if (S.slots.size() < S.max_expanded) {
+    S.slots.emplace_back();
+    idx = (long)S.slots.size() - 1;
+  } else {
+    for (size_t i = 0; i < S.slots.size(); i++)
+      if (S.slots[i].pins == 0 && (idx < 0 || S.slots[i].used < S.slots[(size_t)idx].used)) idx = (long)i;
+  }
+  if (idx >= 0 && !S.slots[(size_t)idx].owner.empty()) {
+    S.evictions++;
+    S.slot_of.erase(S.slots[(size_t)idx].owner);
+    S.slots[(size_t)idx].owner.clear();
+    S.slots[(size_t)idx].used = 0;
+  }
+  return idx;
+}
+// ... and `image` expanded into it (caller holds reg_mu); a failure leaves the slot nobody's
+static void fill_slot(sp_server::Slot& sl, const sp_ppc_t* image) {
+  if (!sl.pp) {
+    sl.pp = expand_pp(image);
+  } else if (sp_pp_expand_into(image, sl.pp.get()) != SP_OK) {
+    throw Fail{SP_E_ARG, std::string("sp_pp_expand_into: ") + sp_last_error()};
+  }
+}
+
+// the expanded parameters of client `uuid` for one request: a hit, a miss or an overflow (sp_server_set_expanded_clients)
+static std::shared_ptr<sp_pp_t> expanded_client(sp_server& S, const std::string& uuid, int i, Pins& pins) {
+  std::shared_ptr<sp_ppc_t> image;
+  {
+    std::lock_guard<std::mutex> lk(S.reg_mu);
+    auto c = S.compact.find(uuid);
+    if (c == S.compact.end()) throw Fail{SP_E_NOTFOUND, "request " + std::to_string(i) + ": unknown uuid " + uuid};
+    auto it = S.slot_of.find(uuid);
+    if (it != S.slot_of.end()) {
+      sp_server::Slot& sl = S.slots[it->second];
+      S.hits++;
+      sl.pins++;
+      sl.used = ++S.clock;
+      pins.held.push_back(it->second);
+      return sl.pp;
+    }
+    const long idx = take_slot(S);
+    if (idx >= 0) {
+      sp_server::Slot& sl = S.slots[(size_t)idx];
+      fill_slot(sl, c->second.get());
+      S.misses++;
+      sl.owner = uuid;
+      S.slot_of[uuid] = (size_t)idx;
+      sl.pins++;
+      sl.used = ++S.clock;
+      pins.held.push_back((size_t)idx);
+      return sl.pp;
+    }
+    S.overflows++;
+    image = c->second;   // (kept past a concurrent forget)
+  }
+  return expand_pp(image.get());   // dies with the request
+}
+
+// direct-upload params with expanded slots: the element's public parameters through the slot's wire buffer into the slot
+static std::shared_ptr<sp_pp_t> expanded_upload(sp_server& S, const uint8_t* data, Pins& pins) {
+  {
+    std::lock_guard<std::mutex> lk(S.reg_mu);
+    const long idx = take_slot(S);
+    if (idx >= 0) {
+      sp_server::Slot& sl = S.slots[(size_t)idx];
+      if (!sl.wire)
+        sl.wire = compact_pp(S, data, S.setup_bytes);
+      else if (sp_ppc_assign_(sl.wire.get(), data, S.setup_bytes) != SP_OK)
+        throw Fail{SP_E_ARG, std::string("public parameters: ") + sp_last_error()};
+      fill_slot(sl, sl.wire.get());
+      S.misses++;
+      sl.pins++;
+      sl.used = ++S.clock;
+      pins.held.push_back((size_t)idx);
+      return sl.pp;
+    }
+    S.overflows++;
+  }
+  return expand_pp(compact_pp(S, data, S.setup_bytes).get());
+}
+
 // the body of private_read for a list of already base64-decoded requests
 static void private_read(sp_server& S, const uint8_t* const* reqs, const size_t* lens, int n, uint8_t* out, size_t stride,
                          size_t* out_lens) {
@@ -213,6 +361,13 @@ static void private_read(sp_server& S, const uint8_t* const* reqs, const size_t*
   std::vector<const sp_pp_t*> pps((size_t)n);
   std::vector<const uint8_t*> qs((size_t)n);
   std::vector<size_t> qlens((size_t)n, S.query_bytes);
+  size_t max_expanded;
+  {
+    std::lock_guard<std::mutex> lk(S.reg_mu);
+    max_expanded = S.max_expanded;
+  }
+  Pins pins(S);   // (released when this function returns or throws: sp_process_query_batch has answered the whole list by then)
+  std::unordered_map<std::string, std::shared_ptr<sp_pp_t>> seen;   // one slot per distinct uuid of the list
   for (int i = 0; i < n; i++) {
     if (S.expand_queries) {
       // bin/server.rs:107-121: uuid || query, the uuid names public parameters uploaded through /setup
@@ -220,16 +375,21 @@ static void private_read(sp_server& S, const uint8_t* const* reqs, const size_t*
         throw Fail{SP_E_ARG, "request " + std::to_string(i) + ": " + std::to_string(lens[i]) + " bytes, expected uuid (36) + query_bytes (" +
                                  std::to_string(S.query_bytes) + ")"};
       const std::string uuid((const char*)reqs[i], UUID_V4_STR_BYTES);
-      std::shared_lock<std::shared_mutex> lk(S.mu);
-      auto it = S.pub_params.find(uuid);
-      if (it == S.pub_params.end()) throw Fail{SP_E_NOTFOUND, "request " + std::to_string(i) + ": unknown uuid " + uuid};  // Error::NotFound
-      keep[i] = it->second;
+      if (max_expanded > 0) {
+        auto s = seen.find(uuid);
+        keep[i] = s != seen.end() ? s->second : (seen[uuid] = expanded_client(S, uuid, i, pins));
+      } else {
+        std::shared_lock<std::shared_mutex> lk(S.mu);
+        auto it = S.pub_params.find(uuid);
+        if (it == S.pub_params.end()) throw Fail{SP_E_NOTFOUND, "request " + std::to_string(i) + ": unknown uuid " + uuid};  // Error::NotFound
+        keep[i] = it->second;
+      }
       qs[i] = reqs[i] + UUID_V4_STR_BYTES;
     } else {
       // bin/server.rs:123-138: the public parameters travel with the query
       if (lens[i] != S.setup_bytes + S.query_bytes)
         throw Fail{SP_E_ARG, "request " + std::to_string(i) + ": expected setup_bytes + query_bytes"};
-      keep[i] = deserialize_pp(S, reqs[i], S.setup_bytes);
+      keep[i] = max_expanded > 0 ? expanded_upload(S, reqs[i], pins) : deserialize_pp(S, reqs[i], S.setup_bytes);
       qs[i] = reqs[i] + S.setup_bytes;
     }
     pps[i] = keep[i].get();
@@ -263,18 +423,47 @@ void sp_server_free(sp_server_t* s) { delete s; }
 size_t sp_server_clients(const sp_server_t* s) {
   if (!s) return 0;
   std::shared_lock<std::shared_mutex> lk(s->mu);
-  return s->pub_params.size();
+  std::lock_guard<std::mutex> reg(s->reg_mu);
+  return s->pub_params.size() + s->compact.size();
+}
+
+int sp_server_set_expanded_clients(sp_server_t* s, size_t max_expanded) {
+  return guarded_ep([&] {
+    if (!s) throw Fail{SP_E_ARG, "null argument"};
+    std::shared_lock<std::shared_mutex> lk(s->mu);
+    std::lock_guard<std::mutex> reg(s->reg_mu);
+    if (!s->pub_params.empty() || !s->compact.empty())
+      throw Fail{SP_E_ARG, "sp_server_set_expanded_clients: the server has clients (set it before the first /setup)"};
+    if (max_expanded < s->slots.size())
+      throw Fail{SP_E_ARG, "sp_server_set_expanded_clients: " + std::to_string(s->slots.size()) + " slots are allocated already"};
+    s->slots.reserve(max_expanded);
+    s->max_expanded = max_expanded;
+  });
+}
+
+int sp_server_client_stats(const sp_server_t* s, uint64_t out[7]) {
+  return guarded_ep([&] {
+    if (!s || !out) throw Fail{SP_E_ARG, "null argument"};
+    std::shared_lock<std::shared_mutex> lk(s->mu);
+    std::lock_guard<std::mutex> reg(s->reg_mu);
+    uint64_t bytes = 0;
+    for (const auto& kv : s->pub_params) bytes += sp_pp_device_bytes(kv.second.get());
+    for (const auto& kv : s->compact) bytes += sp_ppc_device_bytes(kv.second.get());
+    for (const auto& sl : s->slots) bytes += sp_pp_device_bytes(sl.pp.get()) + sp_ppc_device_bytes(sl.wire.get());
+    out[0] = s->pub_params.size() + s->compact.size();
+    out[1] = s->pub_params.size() + s->slot_of.size();
+    out[2] = s->hits;
+    out[3] = s->misses;
+    out[4] = s->evictions;
+    out[5] = s->overflows;
+    out[6] = bytes;
+  });
 }
 
 int sp_server_setup(sp_server_t* s, const uint8_t* pp_bytes, size_t len, char* uuid_out37) {
   return guarded_ep([&] {
     if (!s || !pp_bytes || !uuid_out37) throw Fail{SP_E_ARG, "null argument"};
-    auto pp = deserialize_pp(*s, pp_bytes, len);
-    const std::string id = uuid_v4();
-    {
-      std::unique_lock<std::shared_mutex> lk(s->mu);
-      s->pub_params[id] = std::move(pp);
-    }
+    const std::string id = register_client(*s, pp_bytes, len);
     memcpy(uuid_out37, id.c_str(), UUID_V4_STR_BYTES + 1);
   });
 }
@@ -282,8 +471,19 @@ int sp_server_setup(sp_server_t* s, const uint8_t* pp_bytes, size_t len, char* u
 int sp_server_forget(sp_server_t* s, const char* uuid) {
   return guarded_ep([&] {
     if (!s || !uuid) throw Fail{SP_E_ARG, "null argument"};
-    std::unique_lock<std::shared_mutex> lk(s->mu);
-    if (s->pub_params.erase(uuid) == 0) throw Fail{SP_E_NOTFOUND, std::string("unknown uuid ") + uuid};
+    {
+      std::unique_lock<std::shared_mutex> lk(s->mu);
+      if (s->pub_params.erase(uuid) != 0) return;
+    }
+    // a compact client: the image goes; its slot, if it has one, is nobody's and is recycled first, once no request pins it
+    std::lock_guard<std::mutex> reg(s->reg_mu);
+    if (s->compact.erase(uuid) == 0) throw Fail{SP_E_NOTFOUND, std::string("unknown uuid ") + uuid};
+    auto it = s->slot_of.find(uuid);
+    if (it != s->slot_of.end()) {
+      s->slots[it->second].owner.clear();
+      s->slots[it->second].used = 0;
+      s->slot_of.erase(it);
+    }
   });
 }
 
@@ -298,12 +498,7 @@ int sp_server_setup_json(sp_server_t* s, const char* body, size_t body_len, char
     std::vector<uint8_t> raw;
     if (!b64_decode(b64.data(), b64.size(), raw)) throw Fail{SP_E_ARG, "/setup body is not valid base64"};
     char id[UUID_V4_STR_BYTES + 1];
-    auto pp = deserialize_pp(*s, raw.data(), raw.size());
-    const std::string u = uuid_v4();
-    {
-      std::unique_lock<std::shared_mutex> lk(s->mu);
-      s->pub_params[u] = std::move(pp);
-    }
+    const std::string u = register_client(*s, raw.data(), raw.size());
     memcpy(id, u.c_str(), UUID_V4_STR_BYTES + 1);
     const std::string resp = std::string("{\"uuid\":\"") + id + "\"}";  // serde_json::to_string(&UuidResponse { uuid })
     if (resp.size() + 1 > out_cap) throw Fail{SP_E_ARG, "output buffer too small"};

@@ -359,6 +359,19 @@ struct CopyWordsDesc {  // launch_copy_words
   const u32* src;
   size_t n_words;
 };
+// k_pp_raw_image (pp_raw_image.hpp): the raw polynomials of a client's public parameters from the wire image on the device.
+// table[poly]: keystream from u64 word X of the seed's ChaCha20 stream (X % 8 == 0), or PP_RAW_WIRE | Y = the N wire words from u64
+// word Y of the image (the seed is words 0 .. 3).  modulus != 0: keystream words become modulus - (ks % modulus), modulus_inv =
+// floor(2^64 / modulus); modulus == 0: the keystream itself (sp_debug_chacha20_u64_device).  dst[poly * N + k] for words below n_words.
+constexpr u64 PP_RAW_WIRE = 1ull << 63;
+struct PpRawDesc {
+  u64* dst;
+  const u64* wire;   // the image: its first 32 bytes are the key
+  const u64* table;
+  u64 n_words;
+  u64 modulus, modulus_inv;
+};
+void launch_pp_raw_image(const PpRawDesc& d, int n_polys, hipStream_t s);  // elementwise.hip
 
 // ---- database sweep (server.rs:155-221) -----------------------------------------------------
 // Device DB layout per plane: [z][j_local][ii] u64 (word = lo28 | hi28<<32): the reference's

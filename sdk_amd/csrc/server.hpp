@@ -164,6 +164,20 @@ struct DeviceState {
   size_t v1_shift_src = 0;   // [e]  poly index of prod[b(r=1)][0]
   size_t v1_rot_dst = 0, v1_rot_a = 0, v1_rot_b = 0;  // [2e] P2[e][1] += P[b1][2], P2[e][2] += P[b1][1]
   size_t v1_sum_dst = 0, v1_sum_a = 0, v1_sum_b = 0;  // [3e] result[inst][rr][c] = P[b0][rr] + P2[e][rr]
+  // sp_pp_expand / sp_pp_expand_into (capi_compact.hpp): the per-polynomial table of k_pp_raw_image (kernels.hpp, PpRawDesc), built
+  // once; the raw image every expansion on this device is staged in (n_polys * N words, allocated with the table and kept); and the
+  // stream the expansions run on.  One expansion at a time: `mu` is held from the first launch to the end of the wait.
+  struct PpExpand {
+    std::mutex mu;
+    DevBuf<u64> table, raw;
+    hipStream_t stream = nullptr;
+    ~PpExpand() {
+      if (stream) {
+        (void)hipStreamSynchronize(stream);
+        (void)hipStreamDestroy(stream);
+      }
+    }
+  } pp_expand;
 };
 
 struct Workspace;
@@ -194,6 +208,13 @@ struct sp_pp {
   // r06: `all` once more in WAVE layout (k_mats_to_wave, same polynomial order) for k_expand_wave, followed by one more slot that
   // holds the constant polynomials 0 and 1 (N words each); empty when the parameters have no query expansion
   spiral::DevBuf<spiral::u32> all_w;
+};
+
+// a client's public parameters as sent: the wire image on the device, nothing expanded (sp_pp_compact)
+struct sp_ppc {
+  const sp_params* params = nullptr;
+  int device = -1;
+  spiral::DevBuf<uint8_t> image;  // setup_bytes: seed (32 bytes), then the rows >= 1 of every matrix in wire order
 };
 
 struct sp_db {

@@ -70,6 +70,16 @@ def lib():
         L.sp_pp_deserialize.restype = C.c_void_p
         L.sp_pp_deserialize.argtypes = [C.c_void_p, u8p, C.c_size_t]
         L.sp_pp_free.argtypes = [C.c_void_p]
+        L.sp_pp_device_bytes.restype = C.c_size_t
+        L.sp_pp_device_bytes.argtypes = [C.c_void_p]
+        L.sp_pp_compact.restype = C.c_void_p
+        L.sp_pp_compact.argtypes = [C.c_void_p, u8p, C.c_size_t]
+        L.sp_ppc_free.argtypes = [C.c_void_p]
+        L.sp_ppc_device_bytes.restype = C.c_size_t
+        L.sp_ppc_device_bytes.argtypes = [C.c_void_p]
+        L.sp_pp_expand.restype = C.c_void_p
+        L.sp_pp_expand.argtypes = [C.c_void_p]
+        L.sp_pp_expand_into.argtypes = [C.c_void_p, C.c_void_p]
         L.sp_query_begin.restype = C.c_void_p
         L.sp_query_begin.argtypes = [C.c_void_p, C.c_void_p, u8p, C.c_size_t]
         L.sp_query_free.argtypes = [C.c_void_p]
@@ -345,6 +355,15 @@ class PublicParameters:
             raise SpiralError(_err())  # reference: assert_eq!(params.setup_bytes(), data.len())
         return cls(params, h)
 
+    @classmethod
+    def compact(cls, params, data):
+        """the same bytes kept as the wire image on the device (sp_pp_compact): a CompactPublicParameters, expanded on demand"""
+        return CompactPublicParameters(params, data)
+
+    def device_bytes(self):
+        """what the expanded handle keeps on the device (sp_pp_device_bytes)"""
+        return int(lib().sp_pp_device_bytes(_vp(self.h)))
+
     def __del__(self):
         try:
             if getattr(self, "h", None) and not _finalizing():
@@ -360,6 +379,43 @@ class PublicParameters:
         n = C.c_size_t(0)
         _chk(lib().sp_pp_export(_vp(self.h), _p(out), C.c_size_t(cap), C.byref(n)))
         return out[:n.value].copy()
+
+
+class CompactPublicParameters:
+    """A client's public parameters as sent, resident on the device and not expanded (sp_pp_compact): about a quarter of the
+    expanded handle.  expand() / expand_into(pp) run the device-side inverse of the wire format and give, word for word, what
+    PublicParameters.deserialize gives for the same bytes."""
+
+    def __init__(self, params, data):
+        d = _bytes(data)
+        self.params = params
+        self.h = lib().sp_pp_compact(_vp(params.h), _p(d, u8p), C.c_size_t(d.size))
+        if not self.h:
+            raise SpiralError(_err())
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and not _finalizing():
+                lib().sp_ppc_free(_vp(self.h))
+                self.h = None
+        except Exception:
+            pass
+
+    def device_bytes(self):
+        return int(lib().sp_ppc_device_bytes(_vp(self.h)))
+
+    def expand(self):
+        """a fresh PublicParameters (sp_pp_expand)"""
+        h = lib().sp_pp_expand(_vp(self.h))
+        if not h:
+            raise SpiralError(_err())
+        return PublicParameters(self.params, h)
+
+    def expand_into(self, pp):
+        """overwrite the expanded handle `pp` (same params and device) with this client: nothing is allocated or freed on the
+        device.  The caller sees to it that no query reading `pp` is in flight.  Returns `pp`."""
+        _chk(lib().sp_pp_expand_into(_vp(self.h), _vp(pp.h)))
+        return pp
 
 
 class Query:
@@ -906,6 +962,17 @@ class Server:
 
     def clients(self):
         return int(lib().sp_server_clients(_vp(self.h)))
+
+    def set_expanded_clients(self, k):
+        """k > 0 (only while the server has no clients): /setup keeps each client as its compact wire image, at most k clients
+        are expanded at a time, on demand, into slots the server keeps; 0: every client is expanded at /setup (the default)"""
+        _chk(lib().sp_server_set_expanded_clients(_vp(self.h), C.c_size_t(k)))
+
+    def client_stats(self):
+        """dict: registered, expanded, hits, misses, evictions, overflows, device_bytes (compact images plus slots)"""
+        out = (C.c_uint64 * 7)()
+        _chk(lib().sp_server_client_stats(_vp(self.h), out))
+        return dict(zip(("registered", "expanded", "hits", "misses", "evictions", "overflows", "device_bytes"), (int(v) for v in out)))
 
     def setup(self, pp_bytes):
         """/setup on the decoded bytes -> uuid string"""
