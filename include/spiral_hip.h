@@ -276,6 +276,40 @@ int sp_db_digest(const sp_db_t*, uint64_t seed, int which, int plane0, int nplan
  * their primes as the loaders do.  No device call: works with no GPU present.  A host that streams a database through
  * sp_db_load_plane accumulates this beside the upload and compares with sp_db_digest afterwards. */
 int sp_db_digest_ref_words(const sp_params_t*, uint64_t seed, int plane, int z0, int nz, const uint64_t* words, uint64_t acc[2]);
+/* Per-ITEM digests of the resident words: which items differ, where sp_db_digest says whether any does.  Computed on the device in about
+ * one pass over the rows of the range, 16 bytes per item back instead of db_item_size.  The keys are those of sp_db_digest (mix, s_l,
+ * A_l, R_l above), w(plane, z, ii, j) is the canonical word sp_db_read_ref returns (0 for a word the handle does not hold), all
+ * arithmetic mod 2^64.  For item i = j * num_per + ii, lane l in {0, 1} and the plane range P = [plane0, plane0 + nplanes):
+ *     E_l(i) = R_l(j) * sum over plane in P, z in [0, N) of  A_l((plane * N + z) * num_per + ii) * w(plane, z, ii, j)
+ * out[2k], out[2k + 1] = (E_0, E_1) of item item0 + k.  Consequences: the sum over ALL items of E_l is the sum over P of sp_db_digest's
+ * D_l[plane] (wrapping); an all-zero item digests to (0, 0); the tables of the shards of a bucket, added lane by lane, are the unsharded
+ * table; changing one word changes both lanes of exactly one item; every resident format, the batch copy, every shard kind and a sparse
+ * bucket give the same table for the same contents.
+ * present[k] (may be NULL) has the meaning it has in sp_db_read_items: a dense handle holds the items of its rows and columns, all-zero
+ * ones included; a sparse handle the items in its store.  An item not held reads as (0, 0) with present 0: on a sparse bucket the flag
+ * is what separates "absent" from "stored and all zero".
+ * which: SP_DIGEST_RESIDENT or SP_DIGEST_BATCH_COPY, with the pinning rule of sp_db_digest; the call never builds a copy and returns
+ * SP_E_STATE, `out` untouched, when none stands.  count == 0 or nplanes == 0: SP_OK, nothing written.  A bad plane range,
+ * item0 + count > num_items, a null `out` or an unknown `which`: SP_E_ARG, nothing enqueued, nothing written.  out and present are
+ * written only once the whole call has succeeded.
+ * Read-only, threading as sp_db_digest: beside queries and other readers, not beside a writer; it takes its turn at the handle's read
+ * buffer and stream.  A sparse store is summed under one snapshot of its key map, taken on the host; the handle's lock is never held
+ * across device work.  Everything the call needs -- the table of 16 bytes per item of a window, the row keys, a sparse window's flags
+ * and slot list -- is sized before its first kernel and lives in the read buffer; nothing is allocated or freed between kernels.  A
+ * range whose table would exceed db_load_window is cut into windows of whole rows (at least one row), each reading only its own rows.
+ * A dense call reads the rows item0 / num_per .. (item0 + count - 1) / num_per of the plane range and nothing else -- with the
+ * granularity of the resident form: the other row of a PACKED row pair, the other rows of a digit-planar 8-row half group share the
+ * bytes of a requested row -- and copies out the requested items only.  One kernel per resident form; the sums of a dense form meet in
+ * the table through wrapping 64-bit atomic adds, so the result does not depend on the order of arrival. */
+int sp_db_item_digests(const sp_db_t*, uint64_t seed, int which, int plane0, int nplanes, size_t item0, size_t count,
+                       uint64_t* out /* 2 * count: E_0, E_1 per item */, uint8_t* present /* count bytes, may be NULL */);
+/* The same table on the HOST, from words in the reference layout: adds into acc[2 * i + l], i = j * num_per + ii over ALL num_items
+ * items, the contribution of rows z0 .. z0 + nz - 1 of one plane, words[z - z0][ii][j] with the full dim0 -- what sp_db_load_plane
+ * takes -- after reducing both 32-bit limbs mod their primes as the loaders do.  No device call.  A host that streams a database
+ * through sp_db_load_plane accumulates the table beside the upload.  Bad coordinates or a null pointer: SP_E_ARG, acc untouched.
+ * nz == 0: SP_OK. */
+int sp_db_item_digests_ref_words(const sp_params_t*, uint64_t seed, int plane, int z0, int nz, const uint64_t* words,
+                                 uint64_t* acc /* 2 * num_items */);
 size_t sp_db_device_bytes(const sp_db_t*);      /* the resident database words */
 size_t sp_db_batch_copy_bytes(const sp_db_t*);  /* the digit-planar copy beside them while it stands (sp_db_prepare_batch), else 0 */
 

@@ -101,6 +101,8 @@ pub mod sys {
         pub fn sp_db_export_rows(db: *const sp_db_t, item0: usize, count: usize, body: *mut u8, body_cap: usize, body_len: *mut usize, records: *mut usize) -> c_int;
         pub fn sp_db_digest(db: *const sp_db_t, seed: u64, which: c_int, plane0: c_int, nplanes: c_int, out: *mut u64) -> c_int;
         pub fn sp_db_digest_ref_words(p: *const sp_params_t, seed: u64, plane: c_int, z0: c_int, nz: c_int, words: *const u64, acc: *mut u64) -> c_int;
+        pub fn sp_db_item_digests(db: *const sp_db_t, seed: u64, which: c_int, plane0: c_int, nplanes: c_int, item0: usize, count: usize, out: *mut u64, present: *mut u8) -> c_int;
+        pub fn sp_db_item_digests_ref_words(p: *const sp_params_t, seed: u64, plane: c_int, z0: c_int, nz: c_int, words: *const u64, acc: *mut u64) -> c_int;
         pub fn sp_db_device_bytes(db: *const sp_db_t) -> usize;
         // ---- PublicParameters (client.rs:146-259)
         pub fn sp_pp_deserialize(p: *const sp_params_t, data: *const u8, len: usize) -> *mut sp_pp_t;
@@ -489,6 +491,18 @@ impl Database {
         })?;
         Ok(out)
     }
+    /// One pair of 64-bit sums per ITEM (`sp_db_item_digests`), items `item0 .. item0 + count` over planes `plane0 .. plane0 + nplanes`,
+    /// and the items' present flags (meaning as in `read_items`): which items differ where `digest` says that some do.  The same table on
+    /// every format; the shards' tables add up (wrapping) to the unsharded one.  `batch_copy` as in `digest`.
+    pub fn item_digests(&self, seed: u64, batch_copy: bool, plane0: usize, nplanes: usize, item0: usize, count: usize) -> Result<(Vec<[u64; 2]>, Vec<u8>), HipError> {
+        let mut out = vec![[0u64; 2]; count];
+        let mut present = vec![0u8; count];
+        check(unsafe {
+            sys::sp_db_item_digests(self.0, seed, batch_copy as c_int, plane0 as c_int, nplanes as c_int, item0, count,
+                                    out.as_mut_ptr() as *mut u64, present.as_mut_ptr())
+        })?;
+        Ok((out, present))
+    }
     pub fn device_bytes(&self) -> usize {
         unsafe { sys::sp_db_device_bytes(self.0) }
     }
@@ -501,6 +515,15 @@ impl Drop for Database {
     fn drop(&mut self) {
         unsafe { sys::sp_db_free(self.0) }
     }
+}
+
+/// The table of `Database::item_digests` on the host (`sp_db_item_digests_ref_words`, no device call): adds into `acc` (2 words per item,
+/// all `num_items` items) the contribution of rows `z0 .. z0 + nz` of one plane, `words[z - z0][ii][j]` with the full `dim0` -- what
+/// `sp_db_load_plane` takes.  `words` must hold `nz` whole z-rows and `acc` 2 * num_items words; the library checks the coordinates only.
+pub fn item_digests_ref_words(params: &Params, seed: u64, plane: usize, z0: usize, nz: usize, words: &[u64], acc: &mut [u64]) -> Result<(), HipError> {
+    check(unsafe {
+        sys::sp_db_item_digests_ref_words(params.0, seed, plane as c_int, z0 as c_int, nz as c_int, words.as_ptr(), acc.as_mut_ptr())
+    })
 }
 
 /// Drop-in for `spiral_rs::server::process_query(params, public_params, query, db)` (server.rs:650-655);

@@ -24,6 +24,7 @@ from .spiral import (
     SpiralError,
     build_library,
     coefficient_expansion,
+    differing_items,
     digest_ref_words,
     encode,
     expand_query,
@@ -31,6 +32,7 @@ from .spiral import (
     fold_ciphertexts_fused,
     from_ntt,
     get_v_folding_neg,
+    item_digests_ref_words,
     lib,
     library_path,
     multiply,

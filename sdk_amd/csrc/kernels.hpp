@@ -684,4 +684,31 @@ void launch_digest_sparse(const DigestDesc& d, const u64* polys, int planes, con
 // digit-planar words (a planar-resident handle, a planar row shard `sh`, the batch copy of a PACKED database: sh = {}); sweep_planar.hip
 void launch_digest_planar(const DigestDesc& d, const unsigned char* planar, PlanarShardShape sh, hipStream_t s);
 
+// ---- per-item digests (sp_db_item_digests; db_item_digest.hpp, db_item_digest_planar.hpp, capi_item_digest.hpp) -------------------
+// The keys above, one pair of sums per ITEM i = j * num_per + ii over a plane range P:
+//     E_l(i) = R_l(j) * sum over plane in P, z of A_l((plane * N + z) * num_per + ii) * w(plane, z, ii, j)
+// so the sum over all items of E_l is the sum over P of D_l[plane].  The key that varies along an item's words is the column key (a mix
+// each); the row key multiplies the finished sum once.  A call works on WINDOWS of whole rows: `table` holds the pairs of the window's
+// rows in reference order, table[2 * (r * num_per + ii) + l] for window row r and reference column ii (zeroed by launch_digest_keys,
+// which also writes R[l * nrows + r] = R_l(first global row of the window + r)); the dense kernels add into it with wrapping atomics,
+// columns another shard holds stay 0.
+constexpr int ITEM_DIGEST_Z = 64;   // z-rows one workgroup of a dense kernel walks with its sums in registers
+struct ItemDigestDesc {
+  unsigned long long* table;
+  const u64* R;
+  u64 s[2];
+  int plane0, nplanes;
+  int num_per;      // columns of the REFERENCE
+  int nj;           // the handle's local rows
+  int jl0, nrows;   // the window: local rows jl0 .. jl0 + nrows - 1
+};
+// 8-byte words / the PACKED unit stream (np_local columns, local column il = reference column cm.off + cm.stride * il)
+void launch_item_digest_words(const ItemDigestDesc& d, const u64* db, int np_local, int packed, ColMap cm, hipStream_t s);
+// a sparse store: list[k] = {slot, item} for the n stored items of the window (device memory), whose first item is item_base; the pair
+// of item i is WRITTEN at table[2 * (i - item_base) + l] and present[i - item_base] = 1 (both zeroed by the caller)
+void launch_item_digest_sparse(const ItemDigestDesc& d, const u64* polys, int planes, const DigestSlotRec* list, size_t n,
+                               unsigned long long item_base, uint8_t* present, hipStream_t s);
+// digit-planar words (planar-resident, a planar row shard `sh`, the batch copy: sh = {}); sweep_planar.hip
+void launch_item_digest_planar(const ItemDigestDesc& d, const unsigned char* planar, PlanarShardShape sh, hipStream_t s);
+
 }  // namespace spiral

@@ -11,6 +11,7 @@
 #include "sweep_narrow_batch.hpp"
 #include "planar_resident.hpp"
 #include "db_digest_planar.hpp"
+#include "db_item_digest_planar.hpp"
 #include "server.hpp"
 
 namespace spiral {
@@ -317,6 +318,15 @@ void launch_digest_planar(const DigestDesc& d, const unsigned char* planar, Plan
   const unsigned wgs = (unsigned)std::max<size_t>(1, std::min<size_t>((groups + 255) / 256, std::max<size_t>(4096, groups / (256 * 32))));
   hipLaunchKernelGGL(k_digest_planar, dim3(wgs, d.nplanes), dim3(256), 0, s, d, planar, planar_cols(sh, d.num_per));
   launched(0, "k_digest_planar");
+}
+// sp_db_item_digests over digit-planar words: one thread per half of a (16-row group, column) of the 64-row blocks the window touches
+void launch_item_digest_planar(const ItemDigestDesc& d, const unsigned char* planar, PlanarShardShape sh, hipStream_t s) {
+  if (d.nplanes <= 0 || d.nrows <= 0) return;
+  const int nblk = ((d.jl0 + d.nrows - 1) >> 6) - (d.jl0 >> 6) + 1;
+  const size_t threads = (size_t)(d.num_per >> 7) * 4 * (size_t)nblk * 2 * 64 * 2;
+  hipLaunchKernelGGL(k_item_digest_planar, dim3((unsigned)((threads + 255) / 256), N / ITEM_DIGEST_Z, d.nplanes), dim3(256), 0, s, d, planar,
+                     planar_cols(sh, d.num_per));
+  launched(0, "k_item_digest_planar");
 }
 // The group's query tables for a pass over a planar-resident database (d.planar = its words): one tile's planar tables and offset
 // terms for 1 .. 8 queries, both tiles' for 9 .. 16.  No switch is asked: the handle's format was decided when it was created.

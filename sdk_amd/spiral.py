@@ -619,6 +619,47 @@ class Database:
             raise e
         return out.reshape(-1, 2)[:max(nplanes, 0)]
 
+    def item_digests(self, seed, item0=0, count=None, which="resident", plane0=0, nplanes=None):
+        """one pair of 64-bit sums per ITEM over the resident words of a plane range (sp_db_item_digests), computed on the device in
+        about one pass over the rows of the range -> (uint64 ndarray [count][2], present: uint8 ndarray [count]).  Where digest()
+        says whether two handles differ, two tables say in which items (differing_items).  The same table on every format, shard
+        split and sparse bucket for the same contents; the shards' tables add up (wrapping) to the unsharded one; the lane sums of
+        the whole table are the sums of digest() over the planes.  present as in read_items: an item this handle does not hold reads
+        as (0, 0) with present 0.  which: "resident" or "batch_copy" (SpiralError with rc -4 when no copy stands).  The exception
+        carries the library's `rc`."""
+        code = {"resident": 0, "batch_copy": 1}.get(which, which)
+        if count is None:
+            count = int(self.params.get("num_items")) - item0
+        if nplanes is None:
+            nplanes = self.params.instances * self.params.n * self.params.n - plane0
+        out = np.zeros((max(count, 1), 2), dtype=np.uint64)
+        present = np.zeros(max(count, 1), dtype=np.uint8)
+        rc = lib().sp_db_item_digests(_vp(self.h), C.c_uint64(seed), C.c_int(code), C.c_int(plane0), C.c_int(nplanes),
+                                      C.c_size_t(item0), C.c_size_t(count), _p(out), _p(present, u8p))
+        if rc != 0:
+            e = SpiralError(f"libspiral_hip rc={rc}: {_err()}")
+            e.rc = rc
+            raise e
+        return out[:max(count, 0)], present[:max(count, 0)]
+
+    def repair_from(self, src, seed):
+        """make this handle hold what `src` holds, moving only the items that differ: the two item_digests tables are compared, the
+        differing indices are exported from `src` as runs (export_rows(item0, count) per run of consecutive indices) and applied here
+        with update_rows.  Returns (repaired, not_removable), two sorted index arrays.  not_removable: items this handle holds and
+        `src` does not -- no format has a delete, so they are left alone and reported; on dense handles of one shape there are none.
+        An index a shard of the pair does not hold is skipped by update_rows as ever.  `src` and self are handles of the same Params;
+        neither may be written meanwhile."""
+        da, pa = src.item_digests(seed)
+        db, pb = self.item_digests(seed)
+        diff = differing_items((da, pa), (db, pb))
+        gone = diff[(pa[diff] == 0) & (pb[diff] != 0)]
+        todo = diff[pa[diff] != 0]
+        if todo.size:
+            cuts = np.flatnonzero(np.diff(todo) != 1) + 1
+            for run in np.split(todo, cuts):
+                self.update_rows(src.export_rows(int(run[0]), int(run.size)))
+        return todo, gone
+
     def device_bytes(self):
         return int(lib().sp_db_device_bytes(_vp(self.h)))
 
@@ -641,6 +682,33 @@ def digest_ref_words(params, seed, plane, z0, words, acc=None):
     _chk(lib().sp_db_digest_ref_words(_vp(params.h), C.c_uint64(seed), C.c_int(plane), C.c_int(z0), C.c_int(w.size // per_z), _p(w),
                                       _p(acc)))
     return acc
+
+
+def item_digests_ref_words(params, seed, plane, z0, words, acc=None):
+    """the table of Database.item_digests on the HOST, from reference-layout words (sp_db_item_digests_ref_words; no device call): adds
+    into `acc` (uint64 ndarray [num_items][2], default zeros) the contribution of rows z0 .. z0 + nz - 1 of one plane,
+    words[nz][num_per][dim0] -- what load_plane takes -- with both limbs reduced as the loaders reduce them.  Returns acc."""
+    w = _u64arr(words)
+    per_z = params.num_per * params.dim0
+    if per_z == 0 or w.size % per_z:
+        raise SpiralError("item_digests_ref_words: words are not whole z-rows of num_per * dim0 words")
+    acc = np.zeros((per_z, 2), dtype=np.uint64) if acc is None else acc
+    if acc.dtype != np.uint64 or acc.size != 2 * per_z or not acc.flags.c_contiguous:
+        raise SpiralError("item_digests_ref_words: acc is a C-contiguous uint64 array of 2 * num_items")
+    _chk(lib().sp_db_item_digests_ref_words(_vp(params.h), C.c_uint64(seed), C.c_int(plane), C.c_int(z0), C.c_int(w.size // per_z),
+                                            _p(w), _p(acc)))
+    return acc
+
+
+def differing_items(a, b):
+    """indices where two results of Database.item_digests -- (digests [count][2], present [count]) over the same range -- disagree in
+    either lane or in presence, as a sorted int64 array"""
+    (da, pa), (db, pb) = a, b
+    da, db = np.asarray(da, dtype=np.uint64).reshape(-1, 2), np.asarray(db, dtype=np.uint64).reshape(-1, 2)
+    pa, pb = np.asarray(pa).reshape(-1) != 0, np.asarray(pb).reshape(-1) != 0
+    if da.shape != db.shape or pa.shape != pb.shape or pa.size != da.shape[0]:
+        raise SpiralError("differing_items: the two results cover different ranges")
+    return np.flatnonzero((da != db).any(axis=1) | (pa != pb)).astype(np.int64)
 
 
 def synth_word(seed, ref_index):
