@@ -245,6 +245,31 @@ size_t sp_db_export_rows_bound(const sp_db_t*, size_t count);
  * their responses decode alike, the response bytes may differ.  Threading: as sp_db_read_items. */
 int sp_db_export_rows(const sp_db_t*, size_t item0, size_t count, uint8_t* body, size_t body_cap,
                       size_t* body_len, size_t* records);
+/* Items from one resident database into another, on the device and word for word.  For every item i of [item0, item0 + count) that
+ * `src` holds (`present` of sp_db_read_items) and that `dst`'s shape holds -- the item's row lies in a row shard's rows, its column in a
+ * column shard's columns; a sparse bucket or sparse shard takes the items of its rows (sp_db_create_sparse_shard) -- dst's
+ * 2048 * planes resident words of i become src's canonical words lo | hi << 32 (what sp_db_read_ref returns).  Nothing is decoded and
+ * nothing is encoded again, so unlike dst.update_rows(src.export_rows()) the copy is exact where db_item_size is not a multiple of the
+ * chunk count (the spill coefficients travel), it takes sp_db_fill_synthetic and arbitrary sp_db_load words, and no item byte visits
+ * the host.  Items src does not hold leave dst untouched (one record per held item, the semantics of that pair of calls); a dense src
+ * copies every item it holds, all-zero ones included, into a sparse dst.  Items speak reference coordinates on every format (a planar
+ * row shard's resident column order and a column shard's local columns are undone or applied inside the call).  Every format to every
+ * format: PACKED, 8-byte words, planar-resident, sparse, and row, column, planar and sparse shards in either role; re-sharding on one
+ * device is the intersection of what the two handles hold.  A sparse dst takes new keys in index order, its store grows at most once,
+ * before the call's first kernel, and an existing key is overwritten in its slot.  A PACKED dst beside which a digit-planar batch copy
+ * stands (sp_db_prepare_batch) keeps the copy valid: the touched (16-row group, column) cells are regathered as after
+ * sp_db_update_items.  *copied (may be NULL) = items written.  count == 0: SP_OK, nothing written.
+ * SP_E_ARG, nothing enqueued and nothing written: item0 + count > num_items; a null handle; dst == src; handles made from different
+ * sp_params_t handles; handles on different devices (copies across devices are out of scope).  Any other failure (SP_E_OOM, SP_E_HIP) may
+ * leave dst partly updated -- the windows before the failing one are written -- but a sparse dst never keeps a key whose slot no
+ * launch was issued for: new keys enter its key map window by window, behind the window's launch.
+ * Threading: dst follows the writers' rule (sp_db_update_item: not beside queries or readers of dst); src follows the readers' rule
+ * (sp_db_read_items: beside queries and other readers of src, taking its turn at src's read buffer and stream); a sparse src is read
+ * under one host-side snapshot of its key map, and no lock of src is held across device work.
+ * The staging words and the record lists live in src's read buffer, in windows of at most db_load_window bytes, sized before the first
+ * kernel; per window at most one gather launch (none for a sparse src, whose store is read in place), one scatter launch and, where a
+ * batch copy stands, one patch launch; nothing is allocated or freed between the kernels of a call. */
+int sp_db_copy_items(sp_db_t* dst, const sp_db_t* src, size_t item0, size_t count, size_t* copied /* may be NULL */);
 /* A digest of the resident words, computed on the device in about one database pass: one pair of 64-bit sums per plane
  * (plane = instance * n^2 + trial), defined over REFERENCE coordinates, so every resident format, every shard split and a sparse bucket
  * give the same value for the same contents.  With N = 2048, w(plane, z, ii, j) the canonical word lo | hi << 32 that sp_db_read_ref
@@ -560,6 +585,12 @@ size_t sp_server_private_read_json_bound(const sp_server_t*, int n_queries); /* 
  * reply {"status":"done updating", "loading_time_us":N, "largest_update":M} (NUL-terminated; 128 bytes always suffice).  A faulty
  * record: sp_db_update_rows' status and text, the prefix applied, nothing written to out. */
 int sp_server_update_row(sp_server_t*, sp_db_t* db, const uint8_t* body, size_t body_len, char* out, size_t out_cap, size_t* out_len);
+/* Switch a running server to another database handle -- a bucket moved to another format with sp_db_copy_items, say -- under the write
+ * side of the same lock: lists in flight hold the read side, so a list is answered wholly from the old or wholly from the new handle.
+ * `new_db` must be from the server's params, on the device of the handle it replaces, and unsharded: SP_E_ARG otherwise, and the
+ * server stays as it was.  Afterwards sp_server_update_row insists on new_db.  The old handle stays the caller's to free; new_db is
+ * borrowed as sp_server_create borrows. */
+int sp_server_replace_db(sp_server_t*, const sp_db_t* new_db);
 /* Compact client registry.  max_expanded = 0 (the default): every client is expanded at /setup and stays so until it is forgotten.
  * max_expanded = k > 0 (only while the server has no clients, else SP_E_ARG): /setup keeps the COMPACT handle (sp_pp_compact) only, and
  * the server owns at most k expanded slots, allocated on first use and kept until sp_server_free.  /private-read, per distinct uuid

@@ -99,6 +99,7 @@ pub mod sys {
         pub fn sp_db_read_items(db: *const sp_db_t, item0: usize, count: usize, out: *mut u8, out_cap: usize, present: *mut u8, undecodable: *mut usize) -> c_int;
         pub fn sp_db_export_rows_bound(db: *const sp_db_t, count: usize) -> usize;
         pub fn sp_db_export_rows(db: *const sp_db_t, item0: usize, count: usize, body: *mut u8, body_cap: usize, body_len: *mut usize, records: *mut usize) -> c_int;
+        pub fn sp_db_copy_items(dst: *mut sp_db_t, src: *const sp_db_t, item0: usize, count: usize, copied: *mut usize) -> c_int;
         pub fn sp_db_digest(db: *const sp_db_t, seed: u64, which: c_int, plane0: c_int, nplanes: c_int, out: *mut u64) -> c_int;
         pub fn sp_db_digest_ref_words(p: *const sp_params_t, seed: u64, plane: c_int, z0: c_int, nz: c_int, words: *const u64, acc: *mut u64) -> c_int;
         pub fn sp_db_item_digests(db: *const sp_db_t, seed: u64, which: c_int, plane0: c_int, nplanes: c_int, item0: usize, count: usize, out: *mut u64, present: *mut u8) -> c_int;
@@ -185,6 +186,7 @@ pub mod sys {
         pub fn sp_server_private_read_json_bound(s: *const sp_server_t, n_queries: c_int) -> usize;
         pub fn sp_server_update_row(s: *mut sp_server_t, db: *mut sp_db_t, body: *const u8, body_len: usize, out: *mut c_char,
                                     out_cap: usize, out_len: *mut usize) -> c_int;
+        pub fn sp_server_replace_db(s: *mut sp_server_t, new_db: *const sp_db_t) -> c_int;
         // ---- measurement aids
         pub fn sp_sweep_launches(p: *const sp_params_t, db: *const sp_db_t) -> c_int;
         pub fn sp_bench_sweep(q: *mut sp_query_t, db: *const sp_db_t, iters: c_int, ms_per_launch: *mut f32) -> c_int;
@@ -481,6 +483,14 @@ impl Database {
         body.truncate(len);
         Ok(body)
     }
+    /// The items of the range that `src` holds and this handle's shape holds, copied on the device word for word
+    /// (`sp_db_copy_items`): every format and shard kind to every other, same `Params` and device; exact where
+    /// `update_rows(&src.export_rows(..)?)` is not, and no item byte visits the host.  Returns the items written.
+    pub fn copy_from(&mut self, src: &Database, item0: usize, count: usize) -> Result<usize, HipError> {
+        let mut copied = 0usize;
+        check(unsafe { sys::sp_db_copy_items(self.0, src.0, item0, count, &mut copied) })?;
+        Ok(copied)
+    }
     /// One pair of 64-bit sums per plane over the resident words (`sp_db_digest`), planes `plane0 .. plane0 + nplanes`: the same value on
     /// every format, shard split and sparse bucket for the same contents; the shards' digests add up (wrapping) to the unsharded one.
     /// `batch_copy`: digest the digit-planar copy beside a PACKED database instead (`SP_E_STATE` when none stands).
@@ -746,6 +756,15 @@ impl<'a> Server<'a> {
         check(sys::sp_server_update_row(self.h, self._db.0, body.as_ptr(), body.len(), out.as_mut_ptr() as *mut c_char, out.len(), &mut n))?;
         out.truncate(n);
         Ok(String::from_utf8(out).unwrap())
+    }
+    /// Switch the running server to another handle (`sp_server_replace_db`) -- a bucket that `Database::copy_from` has moved to
+    /// another format, say -- under the write side of the database lock: a list is answered wholly from the old or wholly from the
+    /// new handle.  `db`: unsharded, same `Params` and device, else `SP_E_ARG` and the server stays as it was.  The old `Database`
+    /// stays the caller's.
+    pub fn replace_db(&mut self, db: &'a Database) -> Result<(), HipError> {
+        check(unsafe { sys::sp_server_replace_db(self.h, db.0) })?;
+        self._db = db;
+        Ok(())
     }
 }
 impl<'a> Server<'a> {

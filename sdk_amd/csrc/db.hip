@@ -390,3 +390,4 @@ void launch_sweep_out_to_ref(u64* out, const u32* in, int num_per, hipStream_t s
 #include "item_readback.hpp"   // sp_db_read_items: gather + decode, the item loaders above read backwards
 #include "db_digest.hpp"      // sp_db_digest: the kernels over 8-byte words, PACKED units and a sparse store
 #include "db_item_digest.hpp" // sp_db_item_digests: one pair per item, the same three resident forms
+#include "db_copy.hpp"        // sp_db_copy_items: the gathers' inverses, item-major words into 8-byte words and PACKED units

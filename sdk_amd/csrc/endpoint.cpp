@@ -11,6 +11,8 @@
 // Uses only the public C ABI (include/spiral_hip.h); framing (JSON list of strings, standard base64 with padding,
 // what serde_json / the base64 crate emit) is plain host code.
 #include <array>
+#include <atomic>
+#include <thread>
 #include <cerrno>
 #include <chrono>
 #include <cstring>
@@ -26,6 +28,7 @@
 #include "../../include/spiral_hip.h"
 
 extern "C" void sp_set_last_error_(const char* msg);  // capi.cpp
+extern "C" int sp_db_can_replace_(const sp_params_t* params, const sp_db_t* cur, const sp_db_t* next);  // capi_copy.hpp
 extern "C" int sp_ppc_assign_(sp_ppc_t* c, const uint8_t* data, size_t len);  // capi_compact.hpp: overwrite a compact handle's image
 
 namespace {
@@ -178,6 +181,10 @@ struct sp_server {
   std::unordered_map<std::string, std::shared_ptr<sp_pp_t>> pub_params;
   // bin/server.rs:24 RwLock<SparseDb>: /private-read holds it shared for its whole list (:102), /update-row exclusively (:35)
   mutable std::shared_mutex db_mu;
+  // writers of db_mu that are waiting or at work: a new list stands back while there is one (DbRead), so that lists which overlap without
+  // a gap -- two host threads asking in a loop -- cannot keep /update-row or sp_server_replace_db out for ever (the platform's
+  // reader-writer lock prefers readers)
+  mutable std::atomic<int> db_writers{0};
   // ---- compact registry (sp_server_set_expanded_clients(k > 0)): every client is kept as its wire image on the device, at most
   // max_expanded of them are expanded at a time, into slots the server allocates on first use and keeps.  Everything below is under
   // reg_mu, expansions into slots included: one expansion runs at a time on a device anyway (its staging buffer is the device's one).
@@ -195,6 +202,28 @@ struct sp_server {
   std::unordered_map<std::string, size_t> slot_of;  // the expanded clients
   std::vector<Slot> slots;                          // capacity max_expanded from the start: never reallocated
   uint64_t clock = 0, hits = 0, misses = 0, evictions = 0, overflows = 0;
+};
+
+// the read side of db_mu for one list, taken behind every writer that is waiting
+struct DbRead {
+  std::shared_lock<std::shared_mutex> lk;
+  explicit DbRead(const sp_server& s) : lk(s.db_mu, std::defer_lock) {
+    while (s.db_writers.load(std::memory_order_acquire) > 0) std::this_thread::sleep_for(std::chrono::microseconds(50));
+    lk.lock();
+  }
+};
+// ... and the write side, announced before it is waited for
+struct DbWrite {
+  const sp_server& s;
+  std::unique_lock<std::shared_mutex> lk;
+  explicit DbWrite(const sp_server& srv) : s(srv), lk(srv.db_mu, std::defer_lock) {
+    s.db_writers.fetch_add(1, std::memory_order_acq_rel);
+    lk.lock();
+  }
+  ~DbWrite() {
+    lk.unlock();
+    s.db_writers.fetch_sub(1, std::memory_order_acq_rel);
+  }
 };
 
 template <typename F>
@@ -511,7 +540,7 @@ int sp_server_private_read(sp_server_t* s, const uint8_t* const* requests, const
                            size_t out_stride, size_t* out_lens) {
   return guarded_ep([&] {
     if (!s || n < 0 || (n > 0 && (!requests || !request_lens || !out || !out_lens))) throw Fail{SP_E_ARG, "null argument"};
-    std::shared_lock<std::shared_mutex> db_lk(s->db_mu);
+    DbRead db_lk(*s);
     private_read(*s, requests, request_lens, n, out, out_stride, out_lens);
   });
 }
@@ -537,7 +566,7 @@ int sp_server_private_read_json(sp_server_t* s, const char* body, size_t body_le
     }
     std::vector<uint8_t> resp((size_t)n * s->response_bytes);
     std::vector<size_t> rl((size_t)n, 0);
-    std::shared_lock<std::shared_mutex> db_lk(s->db_mu);
+    DbRead db_lk(*s);
     private_read(*s, reqs.data(), lens.data(), n, resp.data(), s->response_bytes, rl.data());
     std::string js = "[";  // serde_json::to_string(&Vec<String>)
     for (int i = 0; i < n; i++) {
@@ -556,11 +585,11 @@ int sp_server_private_read_json(sp_server_t* s, const char* body, size_t body_le
 int sp_server_update_row(sp_server_t* s, sp_db_t* db, const uint8_t* body, size_t body_len, char* out, size_t out_cap, size_t* out_len) {
   return guarded_ep([&] {
     if (!s || !db || (!body && body_len) || !out || !out_len) throw Fail{SP_E_ARG, "null argument"};
-    if (db != s->db) throw Fail{SP_E_ARG, "/update-row: db is not the handle this server was created on"};
     const auto t0 = std::chrono::steady_clock::now();
     size_t applied = 0, largest = 0;
     {
-      std::unique_lock<std::shared_mutex> db_lk(s->db_mu);  // bin/server.rs:35 data.db.write()
+      DbWrite db_lk(*s);  // bin/server.rs:35 data.db.write()
+      if (db != s->db) throw Fail{SP_E_ARG, "/update-row: db is not the handle this server serves (sp_server_create, sp_server_replace_db)"};
       const int rc = sp_db_update_rows(db, body, body_len, &applied, &largest);
       if (rc != SP_OK) throw Fail{rc, sp_last_error()};
     }
@@ -571,6 +600,17 @@ int sp_server_update_row(sp_server_t* s, sp_db_t* db, const uint8_t* body, size_
     if (resp.size() + 1 > out_cap) throw Fail{SP_E_ARG, "output buffer too small"};
     memcpy(out, resp.c_str(), resp.size() + 1);
     *out_len = resp.size();
+  });
+}
+
+int sp_server_replace_db(sp_server_t* s, const sp_db_t* new_db) {
+  return guarded_ep([&] {
+    if (!s || !new_db) throw Fail{SP_E_ARG, "null argument"};
+    // the write side: every list in flight has been answered from the old handle, every later one reads the new
+    DbWrite db_lk(*s);
+    if (!sp_db_can_replace_(s->params, s->db, new_db))
+      throw Fail{SP_E_ARG, "sp_server_replace_db: new_db must be an unsharded handle of the server's params on the device of the handle it replaces"};
+    s->db = new_db;
   });
 }
 

@@ -595,6 +595,34 @@ struct ItemDecodeDesc {
 };
 void launch_items_decode(const DevTables& T, const ItemDecodeDesc& d, size_t n_items, hipStream_t s);
 
+// ---- item copies between resident databases (sp_db_copy_items; db_copy.hpp, db_copy_planar.hpp, db_copy_sparse.hpp): the gathers above
+// read backwards.  `stage` holds item-major canonical words [index][plane][z] -- a gathered window, or a sparse bucket's store read in
+// place -- and every writer is driven by a device list built per window; a source index < 0 means "this call does not write it".
+// 8-byte words: the written items are the run [D0, D0 + nD) of the handle's local linear index, src_of[L - D0] = stage index or -1
+void launch_items_scatter_words8(u64* db, const u64* stage, const int* src_of, size_t D0, size_t nD, int np_local, int nj, int planes,
+                                 hipStream_t s);
+// PACKED: one entry per touched quad (local row pair jp, local column pair q), src[row a * 2 + column b]; the four words of a quad share
+// a 28-byte lane group, so the caller lists a quad ONCE per launch with every item of it that the launch writes
+struct CopyQuadRec {
+  int jp, q;
+  int src[4];
+};
+void launch_items_scatter_packed(u64* db, const u64* stage, const CopyQuadRec* quads, size_t n_quads, int np_local, int nj, int planes,
+                                 hipStream_t s);
+// digit-planar words (a planar-resident handle or planar row shard `sh`): one entry per touched (16-row group, column) cell -- j = the
+// group's first local row, ii = the REFERENCE column, src[t] for local row j + t -- listed ONCE per launch
+struct CopyCellRec {
+  int j, ii;
+  int src[16];
+};
+void launch_planar_scatter_items(unsigned char* planar, const u64* stage, const CopyCellRec* cells, size_t n_cells, int num_per, int nj,
+                                 int planes, PlanarShardShape sh, hipStream_t s);
+// a sparse bucket's store: polys[slot][plane][z] = stage[src][plane][z]; a slot listed once per launch
+struct CopySlotRec {
+  int src, slot;
+};
+void launch_items_copy_slots(u64* polys, const u64* stage, const CopySlotRec* recs, size_t n_recs, int planes, hipStream_t s);
+
 // ---- sparse buckets (lib/server SparseDb caller; sparse.hip) ----------------------------------------------------------
 // one item's bytes (device) -> `planes` packed NTT polynomials at slot_polys[plane][z]
 void launch_sparse_item_encode(const DevTables& T, const uint8_t* bytes, int item_bytes, int bytes_per_chunk, int logp,

@@ -282,3 +282,5 @@ void launch_sweep_sparse_batch(const DevTables& T, const int* col_ptr, const int
 
 // the same multiplies on a row shard of a sparse bucket, stored in the reduce-scatter layouts
 #include "sweep_sparse_scatter.hpp"
+// sp_db_copy_items into a sparse bucket: item-major words into slots
+#include "db_copy_sparse.hpp"

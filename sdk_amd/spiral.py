@@ -600,6 +600,22 @@ class Database:
             raise e
         return body[:body_len.value].tobytes()
 
+    def copy_from(self, src, item0=0, count=None):
+        """the items of the range that `src` holds and this handle's shape holds, copied on the device word for word
+        (sp_db_copy_items) -> items written.  Every format and shard kind to every other, same Params and device; exact where
+        update_rows(src.export_rows()) is not (spill coefficients, synthetic words), and no item byte visits the host.  This handle
+        follows the writers' rule, `src` the readers'."""
+        if count is None:
+            count = int(self.params.get("num_items")) - item0
+        copied = C.c_size_t(0)
+        rc = lib().sp_db_copy_items(_vp(self.h), _vp(src.h if src is not None else None), C.c_size_t(item0), C.c_size_t(count),
+                                    C.byref(copied))
+        if rc != 0:
+            e = SpiralError(f"libspiral_hip rc={rc}: {_err()}")
+            e.rc = rc
+            raise e
+        return int(copied.value)
+
     def digest(self, seed, which="resident", plane0=0, nplanes=None, out=None):
         """one pair of 64-bit sums per plane over the resident words, computed on the device in about one database pass
         (sp_db_digest) -> uint64 ndarray [nplanes][2].  Defined over reference coordinates: every format, every shard split and a
@@ -1072,14 +1088,32 @@ class Server:
         _chk(lib().sp_server_private_read(_vp(self.h), r_arr, l_arr, C.c_int(n), _p(out, u8p), C.c_size_t(rb), lens))
         return [out[i * rb:i * rb + lens[i]].tobytes() for i in range(n)]
 
-    def update_row(self, body):
+    def update_row(self, body, db=None):
         """/update-row on the HTTP body (bin/server.rs:31-43), applied to the server's database under the write side of its lock
-        -> '{"status":"done updating", "loading_time_us":N, "largest_update":M}'"""
+        -> '{"status":"done updating", "loading_time_us":N, "largest_update":M}'.  db: the handle to write (default: the one the
+        server serves; any other raises SpiralError, SP_E_ARG)"""
         b = np.frombuffer(bytes(body), dtype=np.uint8)
         out = C.create_string_buffer(128)
         n = C.c_size_t(0)
-        _chk(lib().sp_server_update_row(_vp(self.h), _vp(self.db.h), _p(b, u8p), C.c_size_t(b.size), out, C.c_size_t(128), C.byref(n)))
+        h = (self.db if db is None else db).h
+        rc = lib().sp_server_update_row(_vp(self.h), _vp(h), _p(b, u8p), C.c_size_t(b.size), out, C.c_size_t(128), C.byref(n))
+        if rc != 0:
+            e = SpiralError(f"libspiral_hip rc={rc}: {_err()}")
+            e.rc = rc
+            raise e
         return out.raw[:n.value].decode()
+
+    def replace_db(self, db):
+        """switch the running server to another handle (sp_server_replace_db) -- a bucket that Database.copy_from has moved to
+        another format, say -- under the write side of the database lock: a list is answered wholly from the old or wholly from the
+        new handle.  `db`: unsharded, same Params and device, else SpiralError (its `rc`: SP_E_ARG) and the server stays as it was.
+        The old Database stays the caller's."""
+        rc = lib().sp_server_replace_db(_vp(self.h), _vp(db.h))
+        if rc != 0:
+            e = SpiralError(f"libspiral_hip rc={rc}: {_err()}")
+            e.rc = rc
+            raise e
+        self.db = db
 
     def private_read_json(self, body):
         """/private-read on the HTTP body (JSON list of base64 strings) -> JSON list of base64 strings"""
