@@ -270,6 +270,31 @@ int sp_db_export_rows(const sp_db_t*, size_t item0, size_t count, uint8_t* body,
  * kernel; per window at most one gather launch (none for a sparse src, whose store is read in place), one scatter launch and, where a
  * batch copy stands, one patch launch; nothing is allocated or freed between the kernels of a call. */
 int sp_db_copy_items(sp_db_t* dst, const sp_db_t* src, size_t item0, size_t count, size_t* copied /* may be NULL */);
+/* Remove items from a resident database on the device, on every format: PACKED, 8-byte words, planar-resident, sparse, and row, column,
+ * planar and sparse shards.  Items speak reference coordinates on every format; indices a shard does not hold (a row or column outside
+ * its shape) are skipped and not counted.  The list is deduplicated on the host: a repeated index counts once.
+ * A sparse bucket or sparse shard loses the KEY: with n slots in use and m distinct listed keys present, the count becomes n - m,
+ * *removed = m, absent keys are no-ops.  The store stays dense: the survivors at or above slot n - m move, in ascending order, into the
+ * removed slots below it (one launch per window of the move list), sp_db_sparse_items drops by m, `present` of sp_db_read_items /
+ * sp_db_item_digests becomes 0 for the removed keys, and the next query publishes a new index snapshot and pruned expansion plan
+ * (queries begun earlier keep theirs).  Removal never reallocates: sp_db_device_bytes stays (sp_db_sparse_trim gives memory back).
+ * After its last key is removed the bucket behaves as one fresh from sp_db_create_sparse.
+ * A dense handle holds every item of its shape: the item's planes * 2048 words become the empty database's words (zero), `present`
+ * stays 1, *removed = the distinct listed indices the shape holds.  Only the removed items' bytes are touched -- no staging of item
+ * words, no encode; a window of the call is a record list only.  A PACKED handle beside which a digit-planar batch copy stands
+ * (sp_db_prepare_batch) keeps the copy valid: the same items' bytes are cleared in the copy by a second launch of the window.
+ * SP_E_ARG, nothing enqueued and the handle exactly as it was: an index >= num_items anywhere in the list, item0 + count > num_items, a
+ * null handle, a null list with n > 0.  n == 0 / count == 0: SP_OK.  Any other failure (SP_E_HIP) may leave the windows before the
+ * failing one applied, but a sparse bucket never keeps a key that points at a slot whose move was not issued.
+ * Threading: the writers' rule of sp_db_update_item (not beside queries or readers of the handle).  The record lists travel through the
+ * handle's upload buffer in windows of at most db_load_window bytes, sized before the first kernel: one copy in, one launch (two where a
+ * batch copy stands) and one synchronisation per window; nothing is allocated or freed between the kernels of a call. */
+int sp_db_remove_items(sp_db_t*, const size_t* item_idx, size_t n, size_t* removed /* may be NULL */);
+int sp_db_remove_range(sp_db_t*, size_t item0, size_t count, size_t* removed /* may be NULL */);
+/* Give a sparse bucket's unused store back: the store is reallocated to the smallest capacity its growth rule would have chosen for the
+ * current count (64 * 2^k >= count, at least 64 slots) and the live slots are copied across; *freed_bytes = the difference in
+ * sp_db_device_bytes, 0 (and SP_OK) when nothing shrinks.  SP_E_ARG on a handle that is not sparse.  The writers' rule. */
+int sp_db_sparse_trim(sp_db_t*, size_t* freed_bytes /* may be NULL */);
 /* A digest of the resident words, computed on the device in about one database pass: one pair of 64-bit sums per plane
  * (plane = instance * n^2 + trial), defined over REFERENCE coordinates, so every resident format, every shard split and a sparse bucket
  * give the same value for the same contents.  With N = 2048, w(plane, z, ii, j) the canonical word lo | hi << 32 that sp_db_read_ref
@@ -591,6 +616,10 @@ int sp_server_update_row(sp_server_t*, sp_db_t* db, const uint8_t* body, size_t 
  * server stays as it was.  Afterwards sp_server_update_row insists on new_db.  The old handle stays the caller's to free; new_db is
  * borrowed as sp_server_create borrows. */
 int sp_server_replace_db(sp_server_t*, const sp_db_t* new_db);
+/* sp_db_remove_items on the server's database under the write side of the same lock: a list in flight is answered wholly before or
+ * wholly after the removal.  `db` must be the handle the server serves now (sp_server_create, sp_server_replace_db): any other is
+ * SP_E_ARG.  *removed (may be NULL) as sp_db_remove_items. */
+int sp_server_remove_items(sp_server_t*, sp_db_t* db, const size_t* item_idx, size_t n, size_t* removed);
 /* Compact client registry.  max_expanded = 0 (the default): every client is expanded at /setup and stays so until it is forgotten.
  * max_expanded = k > 0 (only while the server has no clients, else SP_E_ARG): /setup keeps the COMPACT handle (sp_pp_compact) only, and
  * the server owns at most k expanded slots, allocated on first use and kept until sp_server_free.  /private-read, per distinct uuid

@@ -100,6 +100,9 @@ pub mod sys {
         pub fn sp_db_export_rows_bound(db: *const sp_db_t, count: usize) -> usize;
         pub fn sp_db_export_rows(db: *const sp_db_t, item0: usize, count: usize, body: *mut u8, body_cap: usize, body_len: *mut usize, records: *mut usize) -> c_int;
         pub fn sp_db_copy_items(dst: *mut sp_db_t, src: *const sp_db_t, item0: usize, count: usize, copied: *mut usize) -> c_int;
+        pub fn sp_db_remove_items(db: *mut sp_db_t, item_idx: *const usize, n: usize, removed: *mut usize) -> c_int;
+        pub fn sp_db_remove_range(db: *mut sp_db_t, item0: usize, count: usize, removed: *mut usize) -> c_int;
+        pub fn sp_db_sparse_trim(db: *mut sp_db_t, freed_bytes: *mut usize) -> c_int;
         pub fn sp_db_digest(db: *const sp_db_t, seed: u64, which: c_int, plane0: c_int, nplanes: c_int, out: *mut u64) -> c_int;
         pub fn sp_db_digest_ref_words(p: *const sp_params_t, seed: u64, plane: c_int, z0: c_int, nz: c_int, words: *const u64, acc: *mut u64) -> c_int;
         pub fn sp_db_item_digests(db: *const sp_db_t, seed: u64, which: c_int, plane0: c_int, nplanes: c_int, item0: usize, count: usize, out: *mut u64, present: *mut u8) -> c_int;
@@ -187,6 +190,7 @@ pub mod sys {
         pub fn sp_server_update_row(s: *mut sp_server_t, db: *mut sp_db_t, body: *const u8, body_len: usize, out: *mut c_char,
                                     out_cap: usize, out_len: *mut usize) -> c_int;
         pub fn sp_server_replace_db(s: *mut sp_server_t, new_db: *const sp_db_t) -> c_int;
+        pub fn sp_server_remove_items(s: *mut sp_server_t, db: *mut sp_db_t, item_idx: *const usize, n: usize, removed: *mut usize) -> c_int;
         // ---- measurement aids
         pub fn sp_sweep_launches(p: *const sp_params_t, db: *const sp_db_t) -> c_int;
         pub fn sp_bench_sweep(q: *mut sp_query_t, db: *const sp_db_t, iters: c_int, ms_per_launch: *mut f32) -> c_int;
@@ -491,6 +495,27 @@ impl Database {
         check(unsafe { sys::sp_db_copy_items(self.0, src.0, item0, count, &mut copied) })?;
         Ok(copied)
     }
+    /// Take the listed items out on the device (`sp_db_remove_items`): a sparse bucket loses the keys and keeps its store dense, a
+    /// dense handle gets the empty database's words in their place.  A repeated index counts once, an index a shard does not hold is
+    /// skipped, an index past `num_items` is `SP_E_ARG` and nothing is written.  Returns the items removed.  The writers' rule.
+    pub fn remove_items(&mut self, indices: &[usize]) -> Result<usize, HipError> {
+        let mut removed = 0usize;
+        check(unsafe { sys::sp_db_remove_items(self.0, indices.as_ptr(), indices.len(), &mut removed) })?;
+        Ok(removed)
+    }
+    /// `remove_items` over `item0 .. item0 + count` (`sp_db_remove_range`).
+    pub fn remove_range(&mut self, item0: usize, count: usize) -> Result<usize, HipError> {
+        let mut removed = 0usize;
+        check(unsafe { sys::sp_db_remove_range(self.0, item0, count, &mut removed) })?;
+        Ok(removed)
+    }
+    /// Shrink a sparse bucket's store to the smallest capacity its growth rule would have chosen for the current count
+    /// (`sp_db_sparse_trim`).  Returns the bytes given back; `SP_E_ARG` on a dense handle.
+    pub fn trim(&mut self) -> Result<usize, HipError> {
+        let mut freed = 0usize;
+        check(unsafe { sys::sp_db_sparse_trim(self.0, &mut freed) })?;
+        Ok(freed)
+    }
     /// One pair of 64-bit sums per plane over the resident words (`sp_db_digest`), planes `plane0 .. plane0 + nplanes`: the same value on
     /// every format, shard split and sparse bucket for the same contents; the shards' digests add up (wrapping) to the unsharded one.
     /// `batch_copy`: digest the digit-planar copy beside a PACKED database instead (`SP_E_STATE` when none stands).
@@ -765,6 +790,13 @@ impl<'a> Server<'a> {
         check(unsafe { sys::sp_server_replace_db(self.h, db.0) })?;
         self._db = db;
         Ok(())
+    }
+    /// `Database::remove_items` on the server's database under the write side of its lock (`sp_server_remove_items`): a list in
+    /// flight is answered wholly before or wholly after the removal.  Returns the items removed.
+    pub fn remove_items(&self, indices: &[usize]) -> Result<usize, HipError> {
+        let mut removed = 0usize;
+        check(unsafe { sys::sp_server_remove_items(self.h, self._db.0, indices.as_ptr(), indices.len(), &mut removed) })?;
+        Ok(removed)
     }
 }
 impl<'a> Server<'a> {

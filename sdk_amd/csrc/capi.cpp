@@ -1613,6 +1613,7 @@ int sp_process_query(const sp_params_t* h, const sp_pp_t* pp, const uint8_t* que
 
 #include "capi_readback.hpp"   // sp_db_read_items, sp_db_export_rows_bound, sp_db_export_rows
 #include "capi_copy.hpp"       // sp_db_copy_items (after capi_readback.hpp: its windows and the read buffer)
+#include "capi_remove.hpp"     // sp_db_remove_items, sp_db_remove_range, sp_db_sparse_trim (after capi_readback.hpp: what a handle holds)
 #include "capi_digest.hpp"     // sp_db_digest, sp_db_digest_ref_words
 #include "capi_item_digest.hpp"   // sp_db_item_digests, sp_db_item_digests_ref_words
 #include "capi_compact.hpp"    // sp_pp_compact, sp_pp_expand, sp_pp_expand_into, sp_pp_device_bytes, sp_debug_chacha20_u64_device

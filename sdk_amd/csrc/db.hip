@@ -391,3 +391,4 @@ void launch_sweep_out_to_ref(u64* out, const u32* in, int num_per, hipStream_t s
 #include "db_digest.hpp"      // sp_db_digest: the kernels over 8-byte words, PACKED units and a sparse store
 #include "db_item_digest.hpp" // sp_db_item_digests: one pair per item, the same three resident forms
 #include "db_copy.hpp"        // sp_db_copy_items: the gathers' inverses, item-major words into 8-byte words and PACKED units
+#include "db_remove.hpp"      // sp_db_remove_items: a removed item's words cleared in 8-byte words and PACKED units

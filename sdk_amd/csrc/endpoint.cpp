@@ -614,4 +614,15 @@ int sp_server_replace_db(sp_server_t* s, const sp_db_t* new_db) {
   });
 }
 
+int sp_server_remove_items(sp_server_t* s, sp_db_t* db, const size_t* item_idx, size_t n, size_t* removed) {
+  if (removed) *removed = 0;
+  return guarded_ep([&] {
+    if (!s || !db || (!item_idx && n)) throw Fail{SP_E_ARG, "null argument"};
+    DbWrite db_lk(*s);   // every list in flight has been answered before the removal, every later one is answered after it
+    if (db != s->db) throw Fail{SP_E_ARG, "sp_server_remove_items: db is not the handle this server serves (sp_server_create, sp_server_replace_db)"};
+    const int rc = sp_db_remove_items(db, item_idx, n, removed);
+    if (rc != SP_OK) throw Fail{rc, sp_last_error()};
+  });
+}
+
 }  // extern "C"

@@ -623,6 +623,31 @@ struct CopySlotRec {
 };
 void launch_items_copy_slots(u64* polys, const u64* stage, const CopySlotRec* recs, size_t n_recs, int planes, hipStream_t s);
 
+// ---- item removal from a resident database (sp_db_remove_items; db_remove.hpp, db_remove_planar.hpp, db_remove_sparse.hpp): a removed
+// item's planes * 2048 words become the empty database's words on the dense forms, and leave a sparse bucket's store.  No staging, no
+// encode: every launch is driven by a device list of records the host builds per window, each record listed ONCE per launch.
+// 8-byte words: locals[k] = the handle's local linear index (item_readback.hpp) of a removed item
+void launch_items_clear_words8(u64* db, const unsigned long long* locals, size_t n, int np_local, int nj, int planes, hipStream_t s);
+// PACKED: one entry per touched quad (local row pair jp, local column pair q); bit (row a * 2 + column b) of mask = that item is removed
+struct RemoveQuadRec {
+  int jp, q;
+  unsigned mask;
+};
+void launch_items_clear_packed(u64* db, const RemoveQuadRec* quads, size_t n_quads, int np_local, int nj, int planes, hipStream_t s);
+// digit-planar words (a planar-resident handle, a planar row shard `sh`, the batch copy of a PACKED handle: sh = {}): one entry per touched
+// (16-row group, column) cell -- j = the group's first local row, ii = the REFERENCE column, bit t of mask = local row j + t is removed
+struct RemoveCellRec {
+  int j, ii;
+  unsigned mask;
+};
+void launch_planar_clear_items(unsigned char* planar, const RemoveCellRec* cells, size_t n_cells, int num_per, int nj, int planes,
+                               PlanarShardShape sh, hipStream_t s);
+// a sparse bucket's store: polys[dst_slot] = polys[src_slot]; the sources and the destinations of a call are disjoint sets
+struct RemoveSlotRec {
+  int src_slot, dst_slot;
+};
+void launch_sparse_move_slots(u64* polys, const RemoveSlotRec* recs, size_t n_recs, int planes, hipStream_t s);
+
 // ---- sparse buckets (lib/server SparseDb caller; sparse.hip) ----------------------------------------------------------
 // one item's bytes (device) -> `planes` packed NTT polynomials at slot_polys[plane][z]
 void launch_sparse_item_encode(const DevTables& T, const uint8_t* bytes, int item_bytes, int bytes_per_chunk, int logp,

@@ -284,3 +284,5 @@ void launch_sweep_sparse_batch(const DevTables& T, const int* col_ptr, const int
 #include "sweep_sparse_scatter.hpp"
 // sp_db_copy_items into a sparse bucket: item-major words into slots
 #include "db_copy_sparse.hpp"
+// sp_db_remove_items on a sparse bucket: survivors moved into the removed slots
+#include "db_remove_sparse.hpp"

@@ -11,6 +11,7 @@
 #include "sweep_narrow_batch.hpp"
 #include "planar_resident.hpp"
 #include "db_copy_planar.hpp"
+#include "db_remove_planar.hpp"
 #include "db_digest_planar.hpp"
 #include "db_item_digest_planar.hpp"
 #include "server.hpp"
@@ -316,6 +317,13 @@ void launch_planar_scatter_items(unsigned char* planar, const u64* stage, const 
   hipLaunchKernelGGL(k_planar_scatter_items, dim3((unsigned)((n_cells + 15) / 16), N / PLANAR_GATHER_Z, planes), dim3(256), 0, s, planar, stage,
                      cells, n_cells, num_per, nj, planes, planar_cols(sh, num_per));
   launched(0, "k_planar_scatter_items");
+}
+void launch_planar_clear_items(unsigned char* planar, const RemoveCellRec* cells, size_t n_cells, int num_per, int nj, int planes,
+                               PlanarShardShape sh, hipStream_t s) {
+  if (n_cells == 0) return;
+  hipLaunchKernelGGL(k_planar_clear_items, dim3((unsigned)((n_cells + 15) / 16), N / PLANAR_CLEAR_Z, planes), dim3(256), 0, s, planar, cells,
+                     n_cells, num_per, nj, planar_cols(sh, num_per));
+  launched(0, "k_planar_clear_items");
 }
 // sp_db_digest over digit-planar words: about 32 sixteen-row groups per thread where the plane has that many, so a workgroup's copy of the
 // row keys is read many times over

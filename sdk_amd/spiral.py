@@ -658,13 +658,43 @@ class Database:
             raise e
         return out[:max(count, 0)], present[:max(count, 0)]
 
-    def repair_from(self, src, seed):
+    def _removed(self, rc, removed):
+        if rc != 0:
+            e = SpiralError(f"libspiral_hip rc={rc}: {_err()}")
+            e.rc = rc
+            raise e
+        return int(removed.value)
+
+    def remove_items(self, indices):
+        """take the listed items out on the device (sp_db_remove_items) -> items removed.  A sparse bucket or sparse shard loses the
+        keys (sparse_items drops, `present` becomes 0, its store stays dense and keeps its size: trim() gives memory back); a dense
+        handle gets the empty database's words in their place.  A repeated index counts once, an index a shard does not hold is
+        skipped, an index >= num_items anywhere in the list raises SpiralError (rc -1) and nothing is written.  The writers' rule."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+        removed = C.c_size_t(0)
+        return self._removed(lib().sp_db_remove_items(_vp(self.h), idx.ctypes.data_as(C.POINTER(C.c_size_t)), C.c_size_t(idx.size),
+                                                      C.byref(removed)), removed)
+
+    def remove_range(self, item0, count=None):
+        """remove_items over item0 .. item0 + count - 1 (sp_db_remove_range; count=None: to the end) -> items removed"""
+        if count is None:
+            count = int(self.params.get("num_items")) - item0
+        removed = C.c_size_t(0)
+        return self._removed(lib().sp_db_remove_range(_vp(self.h), C.c_size_t(item0), C.c_size_t(count), C.byref(removed)), removed)
+
+    def trim(self):
+        """shrink a sparse bucket's store to the smallest capacity its growth rule would have chosen for the current count
+        (sp_db_sparse_trim) -> bytes given back (0 when nothing shrinks).  SpiralError (rc -1) on a dense handle."""
+        freed = C.c_size_t(0)
+        return self._removed(lib().sp_db_sparse_trim(_vp(self.h), C.byref(freed)), freed)
+
+    def repair_from(self, src, seed, remove=False):
         """make this handle hold what `src` holds, moving only the items that differ: the two item_digests tables are compared, the
         differing indices are exported from `src` as runs (export_rows(item0, count) per run of consecutive indices) and applied here
-        with update_rows.  Returns (repaired, not_removable), two sorted index arrays.  not_removable: items this handle holds and
-        `src` does not -- no format has a delete, so they are left alone and reported; on dense handles of one shape there are none.
-        An index a shard of the pair does not hold is skipped by update_rows as ever.  `src` and self are handles of the same Params;
-        neither may be written meanwhile."""
+        with update_rows.  Returns (repaired, gone), two sorted index arrays.  gone: items this handle holds and `src` does not
+        (a sparse bucket's extra keys; on dense handles of one shape there are none) -- left alone and reported by default, taken
+        out with remove_items when remove=True, and returned either way.  An index a shard of the pair does not hold is skipped by
+        update_rows as ever.  `src` and self are handles of the same Params; neither may be written meanwhile."""
         da, pa = src.item_digests(seed)
         db, pb = self.item_digests(seed)
         diff = differing_items((da, pa), (db, pb))
@@ -674,6 +704,8 @@ class Database:
             cuts = np.flatnonzero(np.diff(todo) != 1) + 1
             for run in np.split(todo, cuts):
                 self.update_rows(src.export_rows(int(run[0]), int(run.size)))
+        if remove and gone.size:
+            self.remove_items(gone)
         return todo, gone
 
     def device_bytes(self):
@@ -1114,6 +1146,20 @@ class Server:
             e.rc = rc
             raise e
         self.db = db
+
+    def remove_items(self, db, indices):
+        """Database.remove_items on the server's database under the write side of its lock (sp_server_remove_items) -> items removed:
+        a list in flight is answered wholly before or wholly after the removal.  `db` must be the handle the server serves, else
+        SpiralError (its `rc`: SP_E_ARG)."""
+        idx = np.ascontiguousarray(np.asarray(indices, dtype=np.uint64).reshape(-1))
+        removed = C.c_size_t(0)
+        rc = lib().sp_server_remove_items(_vp(self.h), _vp(db.h), idx.ctypes.data_as(C.POINTER(C.c_size_t)), C.c_size_t(idx.size),
+                                          C.byref(removed))
+        if rc != 0:
+            e = SpiralError(f"libspiral_hip rc={rc}: {_err()}")
+            e.rc = rc
+            raise e
+        return int(removed.value)
 
     def private_read_json(self, body):
         """/private-read on the HTTP body (JSON list of base64 strings) -> JSON list of base64 strings"""
